@@ -2,10 +2,20 @@
 MELD-shaped synthetic batches, GPT-2-small + audio/visual fusion, batch 16 per GPU, bf16 MFMA
 (BASELINE.json configs[1]; with --gpus N one process per GPU over RCCL, configs[2]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-gpu-only]]
 
 Prints ONE JSON line on rank 0.  ``value`` = all utterances processed by all ranks ÷ the max over
-ranks of the wall time of exactly K steps (barrier + device sync on both sides).  ``roofline`` is the
+ranks of the wall time of exactly K steps (barrier + device sync on both sides); ``ms_per_step`` is that
+wall time per step.  A plain run does only this: set up, W warm-up steps, the K timed steps, the line.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller as ``DIR/<name>.npy``
+(float32 / float64; see ``dump_outputs``).  The inputs, the initial weights and the dropout stream are seeded,
+so two runs with the same arguments feed identical inputs and two builds can be compared output for output.
+
+``--full`` adds every measurement that takes steps or time of its own, and their keys in the line: ``roofline``,
+``roofline_secondary``, ``host_enqueue_ms_per_step``, ``gpu_only_ms_per_step`` and ``cpu_baseline`` (the last two
+can be switched off with ``--no-gpu-only`` / ``--no-cpu-baseline``).  ``roofline`` is the
 step's dominant time class, the weight-gradient GEMMs (every Conv1D dW, the stacked caption K/V dW and
 the tied LM-head dW): their algorithmic FLOPs over their in-step launch durations, from HIP event
 pairs the native executor records around each launch in extra steps run right after the timed region
@@ -127,6 +137,42 @@ def cpu_baseline(S, turns, B, model="small", feat_dim=768, seconds_target=20.0):
                       f"GPT-2-{model}+fusion, after 1 warm-up step; torch CPU threads={n}"}
 
 
+DUMP_SAMPLE = 1 << 21  # elements kept of each large output (8 MiB as float32)
+
+
+def dump_outputs(path, out, model, loss_acc, correct, seed=0):
+    """``--dump-outputs``: what the caller of the last timed step holds, as float32 / float64 ``.npy`` files.
+
+    ``loss`` / ``loss_lm`` / ``loss_emotion`` (scalars) and ``emotion_logits`` [B,7] whole; ``logits`` [B,S,V] and
+    the updated fp32 weights (``params``, the flat parameter after the step's AdamW update) as DUMP_SAMPLE elements
+    at fixed flat positions drawn once from a generator seeded with ``seed`` (sorted, with repeats; the same
+    positions in every run of the same shapes); ``train_metrics`` = the accumulated (loss, LM loss, correct
+    emotion predictions) over warm-up and timed steps.  Must run before any further step: the logits are a view
+    of the executor's buffer."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    gen = torch.Generator().manual_seed(seed)
+
+    def sample(t):
+        flat = t.reshape(-1)
+        if flat.numel() <= DUMP_SAMPLE:
+            return flat
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=gen).sort().values
+        return flat[idx.to(flat.device)]
+
+    logits = out.logits_bf16 if out.logits_bf16 is not None else out.logits
+    arrays = {"loss": out.loss, "loss_lm": out.loss_lm, "loss_emotion": out.loss_emotion,
+              "emotion_logits": out.emotion_logits, "logits": sample(logits.detach()),
+              "params": sample(model.flat.detach()),
+              "train_metrics": torch.cat([loss_acc.double().cpu(), correct.double().cpu()])}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as s:
@@ -170,7 +216,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline figure: the roofline probes, the host enqueue "
+                         "cost, the GPU-only step time and the CPU baseline (extra steps after the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle's timing")
     ap.add_argument("--no-overlap-optim", action="store_true",
                     help="apply AdamW in opt.step() instead of per gradient bucket during backward")
     ap.add_argument("--adamw-blocks", type=int, default=None,
@@ -185,12 +236,14 @@ def main():
     ap.add_argument("--defer-update", action="store_true",
                     help="single process: run the block updates after the backward, overlapping the next forward")
     ap.add_argument("--no-gpu-only", dest="gpu_only", action="store_false",
-                    help="skip the extra K steps enqueued behind a spin kernel (no host in the loop) that give "
+                    help="--full: skip the extra K steps enqueued behind a spin kernel (no host in the loop) that give "
                          "gpu_only_ms_per_step")
     ap.add_argument("--pdrop", type=float, default=None,
                     help="attn/resid/embd dropout (default: the config's 0.1, as the reference trains; 0 = off)")
     ap.add_argument("--seed", type=int, default=0, help="torch.manual_seed before the model is built (dropout masks)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     # every ERGM_* variable of this run is recorded in the JSON line (none changes results except the documented
     # data-parallel exchange choices); the library has no knock-out switches, refuse a stale one
     if "ERGM_DIAG_SKIP" in os.environ:
@@ -309,7 +362,9 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    runner = next(iter(model._runners.values()))
+    runner = next(iter(model._runners.values()), None)  # built by the first step
+    if runner is None and args.probe != 5:
+        raise SystemExit("--probe 1..4 times a launch inside the timed steps: needs --warmup >= 1")
     lib = _lib.load()
     import ctypes as C
     # roofline probe: event pairs around every weight-gradient GEMM launch (the dominant time class:
@@ -318,13 +373,13 @@ def main():
     # every timed step
     NPR = 4 * cfg.n_layer * 3 + 8
     n_probe_steps = min(args.steps, 10)
-    if args.probe == 5:
+    if args.probe == 5 and args.full:
         plist = []
         for _ in range(n_probe_steps):
             b, e = [_lib.HipEvent() for _ in range(NPR)], [_lib.HipEvent() for _ in range(NPR)]
             plist.append((b, e, (C.c_void_p * NPR)(*[x.ev.value for x in b]),
                           (C.c_void_p * NPR)(*[x.ev.value for x in e]), (C.c_double * NPR)()))
-    evs = [(_lib.HipEvent(), _lib.HipEvent()) for _ in range(args.steps)]
+    evs = [(_lib.HipEvent(), _lib.HipEvent()) for _ in range(args.steps)] if args.probe != 5 else []
     counts = []
 
     def barrier():
@@ -359,7 +414,7 @@ def main():
         if args.probe != 5:
             e0, e1 = evs[i]
             _lib.check(lib.ergm_model_set_probe(runner.plan, args.probe, e0.ev, e1.ev), "ergm_model_set_probe")
-        step()
+        out = step()
     t_enq = time.perf_counter() - t0  # host time to enqueue the K steps (≈ dt when host-bound)
     if prof is not None:
         prof.disable()
@@ -371,19 +426,25 @@ def main():
     barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    runner = next(iter(model._runners.values()))
     lib.ergm_model_set_probe(runner.plan, 0, None, None)
     metrics = (loss_acc[0].item(), correct.item())  # before any untimed extra step
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model, loss_acc, correct, seed=args.seed)
+    del out
+    # everything from here to the result line that runs further steps is --full's
     # host cost of one step: a few steps enqueued while a spin kernel keeps the device busy, so no launch
     # waits for queue space (in the timed loop the host runs ahead until the queue is full, and from then
     # on its enqueue time is the device's step time)
-    torch.cuda.synchronize()
-    torch.cuda._sleep(int(2.4e9 * 0.15))
-    th = time.perf_counter()
-    for _ in range(3):
-        step()
-    host_ms = round(1000.0 * (time.perf_counter() - th) / 3, 3)
-    torch.cuda.synchronize()
-    if args.probe == 5:
+    if args.full:
+        torch.cuda.synchronize()
+        torch.cuda._sleep(int(2.4e9 * 0.15))
+        th = time.perf_counter()
+        for _ in range(3):
+            step()
+        host_ms = round(1000.0 * (time.perf_counter() - th) / 3, 3)
+        torch.cuda.synchronize()
+    if args.full and args.probe == 5:
         tp = time.perf_counter()
         for pb in plist:
             _lib.check(lib.ergm_model_set_probe_list(runner.plan, 5, pb[2], pb[3], pb[4], NPR), "ergm_model_set_probe_list")
@@ -465,7 +526,8 @@ def main():
                f"256 CUs, bf16 out; the last {Vp - n0} vocabulary columns run as a separate small-tile launch)"
                if n0 < V else "LM-head forward GEMM [T,E]x[E,V] (pipelined MFMA GEMM, bf16 out)")
     lm_flops = 2.0 * T * n0 * E
-    if args.probe == 5:
+    have_roofline = args.full or args.probe != 5  # --probe 1..4 is timed inside the timed steps
+    if args.full and args.probe == 5:
         n_l = len(durs) // max(1, len(counts))
         probe_ms = sum(durs) / len(durs)
         probe_flops = sum(flops) / len(flops)
@@ -478,7 +540,7 @@ def main():
                       "right after the timed region)")
         traffic, traffic_src = pmc_traffic("dw_class", args.config)
         mfma_busy = pmc_mfma_busy("dw_class", args.config)
-    else:
+    elif args.probe != 5:
         probe_flops = {1: lm_flops, 2: 2.0 * T * V * E, 3: 2.0 * T * V * E,
                        4: 2.0 * T * E * (2 * E * cfg.n_layer)}[args.probe]
         probe_name = {1: lm_name, 2: "LM-head dX GEMM", 3: "LM-head dW GEMM", 4: "stacked caption K/V GEMM"}[args.probe]
@@ -507,18 +569,20 @@ def main():
                    "dp_grad_exchange": os.environ["ERGM_DP_GRAD"] + (" (narrower than the reference's fp32 sum)"
                                                                       if os.environ["ERGM_DP_GRAD"] == "bf16" else ""),
                    "dp_sharded_optimizer": os.environ["ERGM_DP_ZERO"] == "1"},
-        "roofline": {"bound": "mfma", "kernel": probe_name, "achieved": round(achieved, 1),
-                     "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                     "traffic": traffic, "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": traffic_src,
-                     "mfma_busy_pmc": mfma_busy,
-                     "avg_launch_ms": round(probe_ms, 4),
-                     "flops_per_launch": probe_flops,
-                     "probe_steps_ms_per_step": round(probe_step_ms, 3) if args.probe == 5 else None},
+        "roofline": ({"bound": "mfma", "kernel": probe_name, "achieved": round(achieved, 1),
+                      "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+                      "traffic": traffic, "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": traffic_src,
+                      "mfma_busy_pmc": mfma_busy,
+                      "avg_launch_ms": round(probe_ms, 4),
+                      "flops_per_launch": probe_flops,
+                      "probe_steps_ms_per_step": round(probe_step_ms, 3) if args.probe == 5 else None}
+                     if have_roofline else None),
         "roofline_secondary": ({"kernel": lm_name, "flops_per_launch": lm_flops, "avg_launch_ms": round(lm_ms, 4),
                                 "achieved": round(lm_flops / (lm_ms * 1e-3) / 1e12, 1),
                                 "frac": round(lm_flops / (lm_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
                                 "traffic": pmc_traffic("lm_head_fwd", args.config)[0],
-                                "timed": "3 extra steps after the timed region"} if args.probe == 5 else None),
+                                "timed": "3 extra steps after the timed region"}
+                               if args.full and args.probe == 5 else None),
         "mfma_step": {"flops_per_step": step_flops, "achieved_tflops": round(step_flops / (ms_step * 1e-3) / 1e12, 1),
                       "frac": round(step_flops / (ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
                       "ceiling_utt_per_s_per_gpu": round(PEAK_BF16_TFLOPS * 1e12 / flops_per_utterance(S, E, Lyr, V),
@@ -536,14 +600,17 @@ def main():
                              if runner.dp.zero else "bf16 all-gather of the reduced gradient")
                             if runner.dp.grad_comm == "bf16" else "fp32 all-reduce"),
                "sharded_optimizer": runner.dp.zero} if world > 1 else None,
-        "host_enqueue_ms_per_step": host_ms,
+        "host_enqueue_ms_per_step": host_ms if args.full else None,
         "host_enqueue_ms_per_step_in_timed_loop": round(1000.0 * t_enq / args.steps, 3),
         # under DP the host also blocks once per step on the compact lookup's row count: the rest is host work
         "host_busy_ms_per_step_in_timed_loop": round(1000.0 * (t_enq - t_sync) / args.steps, 3),
         "train_metrics": {"mean_loss": round(metrics[0] / total, 4),
                           "emotion_acc": round(metrics[1] / (B * total), 4)},
     }
-    if args.gpu_only and world == 1:
+    if not args.full:  # a plain run's line has no key of a measurement it did not make
+        for k in ("roofline_secondary", "host_enqueue_ms_per_step") + (() if have_roofline else ("roofline",)):
+            del rec[k]
+    if args.full and args.gpu_only and world == 1:
         # the same K steps enqueued while the GPU spins: the host is never on the critical path
         torch.cuda.synchronize()
         g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -554,7 +621,7 @@ def main():
         g1.record()
         torch.cuda.synchronize()
         rec["gpu_only_ms_per_step"] = round(g0.elapsed_time(g1) / args.steps, 3)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         rec["cpu_baseline"] = cpu_baseline(S, turns, B, mname, Fd)
     if rank == 0:
         print(json.dumps(rec), flush=True)

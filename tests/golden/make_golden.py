@@ -35,6 +35,9 @@ sys.path.insert(0, REPO)
 from oracle import gpt2_oracle as O  # noqa: E402
 from ergm_amd.data import synthetic_batch  # noqa: E402
 
+sys.path.insert(0, os.path.dirname(HERE))
+from _golden import save_npz  # noqa: E402
+
 REF_SRC = "/root/reference/src"
 
 
@@ -472,7 +475,7 @@ def main():
                  "xpeak_c2": ("xpeak_c2slice.npz", lambda: xpeak_case(refmodel, "xpeak_c2slice"))}
         for c in only:
             fn, make = cases[c]
-            np.savez_compressed(os.path.join(out_dir, fn), **make())
+            save_npz(os.path.join(out_dir, fn), make())  # in parts where one archive would pass 1 MiB
         return
     # 1. tiny, single head (d=64), full grads + one AdamW step: the byte-level fixture
     cfg = O.OracleConfig(vocab_size=256, n_embd=64, n_layer=2, n_head=1, n_positions=64)
@@ -498,7 +501,7 @@ def main():
     np.savez_compressed(os.path.join(out_dir, "dataset_ref.npz"), **dataset_case())
     np.savez_compressed(os.path.join(out_dir, "trainer_ref.npz"), **trainer_case(refmodel))
     # 8. the reference optimizer's per-parameter state (checkpoint interchange)
-    np.savez_compressed(os.path.join(out_dir, "optim_ref.npz"), **optim_case(refmodel))
+    save_npz(os.path.join(out_dir, "optim_ref.npz"), optim_case(refmodel))
     print("golden fixtures written to", out_dir)
 
 

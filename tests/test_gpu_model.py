@@ -15,6 +15,7 @@ from ergm_amd.model import GPT2LMHeadModel
 from ergm_amd.optim import FusedAdamW
 from oracle import gpt2_oracle as O
 from _bitwise import assert_bitwise
+from _golden import load_npz
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -27,8 +28,7 @@ def _rel(a, b):
 
 
 def _load(name):
-    z = np.load(os.path.join(GOLD, name))
-    return {k: z[k] for k in z.files}
+    return load_npz(os.path.join(GOLD, name))
 
 
 def _setup(rec, gpu):

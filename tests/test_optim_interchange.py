@@ -18,13 +18,13 @@ import torch
 
 from ergm_amd.optim import flat_from_reference, reference_from_flat, reference_param_names
 from ergm_amd.params import build_layout
+from _golden import load_npz
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "optim_ref.npz")
 
 
 def _fixture():
-    z = np.load(GOLD)
-    rec = {k: z[k] for k in z.files}
+    rec = load_npz(GOLD)
     order = json.loads(bytes(rec["param_order_json"]).decode())
     group = json.loads(bytes(rec["group_json"]).decode())
     V, E, L, H, P = (int(x) for x in rec["config"])

@@ -10,13 +10,13 @@ import pytest
 import torch
 
 from oracle import gpt2_oracle as O
+from _golden import load_npz
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _load(name):
-    z = np.load(os.path.join(GOLD, name))
-    return {k: z[k] for k in z.files}
+    return load_npz(os.path.join(GOLD, name))
 
 
 def _batch(rec):
@@ -60,7 +60,12 @@ def test_oracle_matches_reference_small(name):
         else:
             ref = float(rec["gradnorm:" + k])
             assert abs(g.double().norm().item() - ref) <= 1e-4 * max(ref, 1e-12), k
-            assert _rel(g.reshape(-1)[:32], rec["gradhead:" + k]) < 1e-3, k
+            # the head against the reference's, down to the fp32 rounding of the tensor itself: elements that
+            # are analytically zero (the key half of a c_attn bias: softmax ignores a shift of its scores) hold
+            # ~1e-12 of summation noise, which depends on the host's thread count and vector width
+            head = torch.from_numpy(rec["gradhead:" + k]).double()
+            d = (g.reshape(-1)[:32].double() - head).norm().item()
+            assert d < 1e-3 * head.norm().item() + torch.finfo(torch.float32).eps * ref, k
 
 
 @pytest.mark.parametrize("name", ["c1_gpt2small_textonly.npz", "c2slice_gpt2small_fusion.npz", "xpeak_c2slice.npz"])
