@@ -13,7 +13,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libergm_hip.so")
 
-ABI_VERSION = 11  # ERGM_ABI_VERSION of include/ergm_hip.h this binding matches
+ABI_VERSION = 12  # ERGM_ABI_VERSION of include/ergm_hip.h this binding matches
 ERGM_OK, ERGM_EINVAL, ERGM_EUNSUPPORTED, ERGM_EHIP = 0, -1, -2, -3
 F32, BF16 = 0, 1
 MK, KM = 0, 1
@@ -37,7 +37,8 @@ class GemmDesc(C.Structure):
                 ("ldc", C.c_int), ("a_layout", C.c_int), ("b_layout", C.c_int), ("c_dtype", C.c_int),
                 ("epilogue", C.c_int), ("alpha", C.c_float), ("bias", C.c_void_p), ("aux", C.c_void_p),
                 ("ld_aux", C.c_int), ("aux_out", C.c_void_p), ("ld_aux_out", C.c_int), ("split_k", C.c_int),
-                ("alpha_dev", C.c_void_p), ("dropout", C.POINTER(Dropout)), ("bias_grad", C.c_void_p)]
+                ("alpha_dev", C.c_void_p), ("dropout", C.POINTER(Dropout)), ("bias_grad", C.c_void_p),
+                ("m_count_dev", C.c_void_p), ("k_count_dev", C.c_void_p), ("row_map", C.c_void_p)]
 
 
 class AdamWDesc(C.Structure):
@@ -101,6 +102,8 @@ _SIGS = {
     "ergm_embed_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]),
     "ergm_count_valid": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "ergm_xent_fwd_bwd": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, f32, vp]),
+    "ergm_lm_rows": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
+    "ergm_xent_compact": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "ergm_emotion_head": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "ergm_loss_finalize": (i32, [vp, i32, vp, vp, vp, vp, vp]),
     "ergm_adamw_step": (i32, [vp, vp, vp, vp, vp, sz, f64, f64, f64, f32, f64, f32, f32, i32, vp]),
@@ -120,6 +123,7 @@ _SIGS = {
     "ergm_model_optimizer_join": (i32, [vp, vp]),
     "ergm_model_set_probe_list": (i32, [vp, i32, vp, vp, vp, i32]),
     "ergm_model_probe_count": (i32, [vp]),
+    "ergm_model_copy_head_dy": (i32, [vp, vp, vp]),
     "ergm_model_set_row_flags": (i32, [vp, vp, i32]),
     "ergm_model_set_lookup_compact": (i32, [vp, vp, vp]),
     "ergm_rows_scan": (i32, [vp, i32, vp, vp, vp]),

@@ -56,9 +56,20 @@ struct GemmArgs {
     uint8_t* q_out;
     uint8_t* q_sc;
     int ld_q, ld_qs;
+    // Device-side extents and the row map of the store (ergm_gemm_desc m_count_dev / k_count_dev / row_map), read
+    // by the DYN kernels only: M and K above are then the capacities the grid and the workspace are sized for.
+    const int* m_dev;
+    const int* k_dev;
+    const int* row_map;
 };
 
-template <int EPI, bool OUT_BF16>
+// DYN kernels: replace the capacities by the extents in device memory (a is the kernel's own copy of its arguments).
+__device__ __forceinline__ void dyn_adjust(GemmArgs& a) {
+    if (a.m_dev) a.M = min(a.M, max(0, *a.m_dev));
+    if (a.k_dev) a.K = min((a.K + GEMM_BK - 1) / GEMM_BK * GEMM_BK, max(0, *a.k_dev));
+}
+
+template <int EPI, bool OUT_BF16, bool DYN = false>
 __device__ __forceinline__ void epilogue_store(const GemmArgs& a, int m, int n, float v) {
     if (EPI == ERGM_EPI_BIAS || EPI == ERGM_EPI_BIAS_GELU || EPI == ERGM_EPI_BIAS_RESID) {
         if (a.bias) v += a.bias[n];
@@ -74,6 +85,9 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& a, int m, int n, 
         v *= bf2f(reinterpret_cast<const __bf16*>(a.aux)[(size_t)m * a.ld_aux + n]);  // stored gelu'(pre)
     }
     size_t idx = (size_t)m * a.ldc + n;
+    if constexpr (DYN) {  // output row m goes to row row_map[m] of C
+        if (a.row_map) idx = (size_t)a.row_map[m] * a.ldc + n;
+    }
     if (OUT_BF16) {
         reinterpret_cast<__bf16*>(a.C)[idx] = f2bf(v);
     } else {
@@ -86,7 +100,7 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& a, int m, int n, 
 // Vectorized epilogue for 8 consecutive columns n..n+7 of row m (N % 8 == 0, n % 8 == 0).
 // pre_bias / pre_aux: the bias (2 float4) and aux operand (BIAS_RESID: 2 float4 of the residual; GELU_BWD: one float4
 // holding 8 bf16) of these 8 columns, loaded before the main loop (EpiPre) — nullptr: loaded here.
-template <int EPI, bool OUT_BF16>
+template <int EPI, bool OUT_BF16, bool DYN = false>
 __device__ __forceinline__ void epilogue_store8(const GemmArgs& a, int m, int n, float* v,
                                                 const float4* pre_bias = nullptr, const float4* pre_aux = nullptr) {
     if (EPI == ERGM_EPI_BIAS || EPI == ERGM_EPI_BIAS_GELU || EPI == ERGM_EPI_BIAS_RESID) {
@@ -123,7 +137,10 @@ __device__ __forceinline__ void epilogue_store8(const GemmArgs& a, int m, int n,
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] *= bf2f(x[j]);
     }
-    const size_t idx = (size_t)m * a.ldc + n;
+    size_t idx = (size_t)m * a.ldc + n;
+    if constexpr (DYN) {
+        if (a.row_map) idx = (size_t)a.row_map[m] * a.ldc + n;
+    }
     if (OUT_BF16) {
         bf16x8 o;
 #pragma unroll
@@ -198,7 +215,7 @@ struct EpiPre {
 // MF: the accumulator fragments' MFMA shape — 16 (f32x4 per 16x16 fragment: lane l holds rows 4(l>>4)+r of column
 // l&15) or 32 (f32x16 per 32x32 fragment: lane l holds rows (r&3) + 8(r>>2) + 4(l>>5) of column l&31).
 template <int BM, int BN, int WGM, int WGN, int EPI, bool OUT_BF16, int FM, int FN, int NT = 64 * WGM * WGN,
-          bool RS = false, bool QMX = false, int MF = 16, typename AccT = f32x4>
+          bool RS = false, bool QMX = false, int MF = 16, typename AccT = f32x4, bool DYN = false>
 __device__ __forceinline__ void store_tile(const GemmArgs& a, char* lds, AccT (&acc)[FM][FN], int m0, int n0,
                                            float alpha, float* slab, const EpiPre<EPI, BM, BN, WGM, NT>* pre = nullptr) {
     // NT: every thread of the workgroup (a warp-specialised kernel adds producer waves, which only
@@ -277,11 +294,11 @@ __device__ __forceinline__ void store_tile(const GemmArgs& a, char* lds, AccT (&
                 if constexpr (EpiPre<EPI, BM, BN, WGM, NT>::ON) {
                     if (pre) {  // c == threadIdx.x: this thread's chunk of pass `pass`, loaded before the K loop
                         constexpr int PER = EpiPre<EPI, BM, BN, WGM, NT>::PER;
-                        epilogue_store8<EPI, OUT_BF16>(a, m, n, v, pre->bias, pre->aux + PER * pass);
+                        epilogue_store8<EPI, OUT_BF16, DYN>(a, m, n, v, pre->bias, pre->aux + PER * pass);
                         continue;
                     }
                 }
-                epilogue_store8<EPI, OUT_BF16>(a, m, n, v);
+                epilogue_store8<EPI, OUT_BF16, DYN>(a, m, n, v);
             }
         }
     }
@@ -328,8 +345,9 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return base + idx;
 }
 
-template <int BM, int BN, bool A_KM, bool B_KN, int EPI, bool OUT_BF16>
+template <int BM, int BN, bool A_KM, bool B_KN, int EPI, bool OUT_BF16, bool DYN = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(GemmArgs a) {
+    if constexpr (DYN) dyn_adjust(a);
     constexpr int WM = BM / 2, WN = BN / 2;
     constexpr int FM = WM / 16, FN = WN / 16;
     constexpr int A_BYTES = BM * GEMM_BK * 2, B_BYTES = BN * GEMM_BK * 2;
@@ -342,9 +360,12 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(GemmArgs a) {
     if (a.sweep_m) { tm = id % a.tiles_m; tn = id / a.tiles_m; }
     else { tn = id % a.tiles_n; tm = id / a.tiles_n; }
     const int m0 = tm * BM, n0 = tn * BN;
+    if constexpr (DYN) {
+        if (m0 >= a.M) return;  // a tile past the device-side row count: nothing to compute or store
+    }
     const int kbeg = blockIdx.z * a.k_per_split;
     const int kend = min(a.K, kbeg + a.k_per_split);
-    const int nk = (kend - kbeg + GEMM_BK - 1) / GEMM_BK;
+    const int nk = max(0, kend - kbeg + GEMM_BK - 1) / GEMM_BK;
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int wm = wave >> 1, wn = wave & 1;
@@ -395,7 +416,8 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(GemmArgs a) {
     if (a.alpha_dev) alpha *= *a.alpha_dev;
     float* slab = a.slab ? a.slab + (size_t)blockIdx.z * a.M * a.N : nullptr;
     if (a.N % 8 == 0 && (a.slab || a.ldc % 8 == 0)) {
-        store_tile<BM, BN, 2, 2, EPI, OUT_BF16, FM, FN>(a, smem, acc, m0, n0, alpha, slab);
+        store_tile<BM, BN, 2, 2, EPI, OUT_BF16, FM, FN, GEMM_THREADS, false, false, 16, f32x4, DYN>(a, smem, acc, m0, n0,
+                                                                                                 alpha, slab);
         return;
     }
     const int lane_ = threadIdx.x & 63, wave_ = threadIdx.x >> 6;
@@ -410,7 +432,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(GemmArgs a) {
                 int m = rbase + i * 16 + r, n = cbase + j * 16;
                 if (m >= a.M || n >= a.N) continue;
                 if (slab) slab[(size_t)m * a.N + n] = acc[i][j][r];
-                else epilogue_store<EPI, OUT_BF16>(a, m, n, alpha * acc[i][j][r]);
+                else epilogue_store<EPI, OUT_BF16, DYN>(a, m, n, alpha * acc[i][j][r]);
             }
 }
 
@@ -424,7 +446,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(GemmArgs a) {
 // MF = 32: v_mfma_f32_32x32x16_bf16 on 32x32 fragments (tile images in swizzle family 1, tiles.h frag32), half the
 // MFMA instructions of the 16x16x32 form for the same wave tile; no in-loop bias sums, staged epilogue only.
 template <int BM, int BN, int WGM, int WGN, int NS, bool A_KM, bool B_KN, int EPI, bool OUT_BF16, bool DIRECT = false,
-          int IL = 0, int MF = 16>
+          int IL = 0, int MF = 16, bool DYN = false>
 __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& a, const int bid) {
     static_assert(MF == 16 || (MF == 32 && !DIRECT && IL == 0), "32x32x16 MFMA: staged epilogue, no interleaved issue");
     constexpr int SW = MF == 32 ? 1 : 0;
@@ -441,16 +463,22 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& a, const int bid)
     const int nwg = a.tiles_m * a.tiles_n;
     // K slice zs: blockIdx.z, or (xcd_split) the XCD the workgroup runs on — workgroup b goes to XCD b % 8,
     // so the tiles of one slice share that XCD's L2 and each operand slice is fetched once
-    const int zs = a.xcd_split ? (bid & 7) : (int)blockIdx.z;
-    const int id = a.xcd_split ? (bid >> 3) : xcd_remap(bid, nwg);
+    // DYN with a device-side row count: only the tiles of the first rows work, and the XCD remap would hand that
+    // contiguous id range to one or two XCDs.  xcd_split there takes 8·gridDim.z slices (slice = XCD + 8·blockIdx.z),
+    // so every XCD gets the same share whatever the count; without it consecutive tiles go round the XCDs.
+    const int zs = a.xcd_split ? (bid & 7) + (DYN ? 8 * (int)blockIdx.z : 0) : (int)blockIdx.z;
+    const int id = a.xcd_split ? (bid >> 3) : (DYN && a.m_dev) ? bid : xcd_remap(bid, nwg);
     if (id >= nwg) return;
     int tm, tn;
     if (a.sweep_m) { tm = id % a.tiles_m; tn = id / a.tiles_m; }
     else { tn = id % a.tiles_n; tm = id / a.tiles_n; }
     const int m0 = tm * BM, n0 = tn * BN;
+    if constexpr (DYN) {
+        if (m0 >= a.M) return;  // a tile past the device-side row count (the whole workgroup leaves, before any barrier)
+    }
     const int kbeg = zs * a.k_per_split;
     const int kend = min(a.K, kbeg + a.k_per_split);
-    const int nk = (kend - kbeg) / GEMM_BK;
+    const int nk = DYN ? max(0, kend - kbeg) / GEMM_BK : (kend - kbeg) / GEMM_BK;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave / WGN, wn = wave % WGN;
 
@@ -585,8 +613,8 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& a, const int bid)
         store_tile_direct<WGN, EPI, OUT_BF16, FM, FN, WM, WN>(a, acc, m0, n0, alpha);
     } else {
         float* slab = a.slab ? a.slab + (size_t)zs * a.M * a.N : nullptr;
-        store_tile<BM, BN, WGM, WGN, EPI, OUT_BF16, FM, FN, 64 * WGM * WGN, false, false, MF>(a, smem, acc, m0, n0, alpha,
-                                                                                           slab, &pre);
+        store_tile<BM, BN, WGM, WGN, EPI, OUT_BF16, FM, FN, 64 * WGM * WGN, false, false, MF, AccT, DYN>(a, smem, acc, m0,
+                                                                                                      n0, alpha, slab, &pre);
     }
 }
 
@@ -709,6 +737,15 @@ template <int BM, int BN, int WGM, int WGN, int NS, bool A_KM, bool B_KN, int EP
           int IL = 0, int MF = 16>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_pipe_kernel(GemmArgs a) {
     gemm_pipe_body<BM, BN, WGM, WGN, NS, A_KM, B_KN, EPI, OUT_BF16, DIRECT, IL, MF>(a, blockIdx.x);
+}
+
+// The pipelined kernel with device-side extents (ergm_gemm_desc m_count_dev / k_count_dev / row_map): f32 out, no
+// epilogue, full tiles and split-K partials alike.  The grid is sized for the capacities; a workgroup whose tile lies
+// past the row count returns at once, and nothing waits for another workgroup.
+template <int BM, int BN, int WGM, int WGN, int NS, bool A_KM, bool B_KN>
+__global__ __launch_bounds__(64 * WGM * WGN) void gemm_pipe_dyn_kernel(GemmArgs a) {
+    dyn_adjust(a);
+    gemm_pipe_body<BM, BN, WGM, WGN, NS, A_KM, B_KN, ERGM_EPI_NONE, false, false, 0, 16, true>(a, blockIdx.x);
 }
 
 // Two weight-gradient GEMMs (KM x KN, f32 out, no split) in ONE launch: workgroups [0, b1) run problem 0
@@ -1006,8 +1043,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_mx_kernel(GemmArgs a) {
 }
 
 // split-K combine: C = epilogue(alpha * Σ_z slab[z]) in z order (deterministic).
-template <int EPI, bool OUT_BF16>
+template <int EPI, bool OUT_BF16, bool DYN = false>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs a, int splits) {
+    if constexpr (DYN) dyn_adjust(a);  // the slabs hold [z][rows][N] of the device-side row count
     size_t total = (size_t)a.M * a.N;
     float alpha = a.alpha;
     if (a.alpha_dev) alpha *= *a.alpha_dev;
@@ -1015,7 +1053,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs a, int spli
         float s = 0.f;
         for (int z = 0; z < splits; ++z) s += a.slab[(size_t)z * total + i];
         int m = (int)(i / a.N), n = (int)(i % a.N);
-        epilogue_store<EPI, OUT_BF16>(a, m, n, alpha * s);
+        epilogue_store<EPI, OUT_BF16, DYN>(a, m, n, alpha * s);
     }
     if (a.colsum && a.colsum_part) {  // the weight-gradient bias: per-split column sums, in z order
         for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < a.N; n += gridDim.x * blockDim.x) {
@@ -1417,6 +1455,85 @@ static void launch_reduce(const GemmArgs& a, int split, hipStream_t s) {
     ERGM_LAUNCH((splitk_reduce_kernel<EPI, OB>), dim3(blocks), dim3(256), 0, s, a, split);
 }
 
+// ---- GEMMs with device-side extents (ergm_gemm_desc m_count_dev / k_count_dev / row_map) -----------------------
+// b_layout KN, epilogue NONE, f32 C.  The pipelined configurations instantiated for them:
+static constexpr bool dyn_cfg_ok(int cfg) { return cfg == 0 || cfg == 2 || cfg == 6 || cfg == 14; }
+
+static bool is_dyn(const ergm_gemm_desc* d) { return d->m_count_dev || d->k_count_dev || d->row_map; }
+
+// Plan for the capacities: the row count is not known on the host, so the tile is the 128x128 one (2-stage ring,
+// two workgroups per CU) and a contraction the host knows is split into ~512-deep slices, 16 at the most: the
+// workgroups of the few tile rows below the row count then number enough to fill the chip (LM-head dX at 415 rows
+// of 2048: 4 x 6 x 16 = 384).  A device-side contraction length is never split.  In-step A/B of cfg 0 / 2 / 14,
+// 8 / 16 slices and the two tile-to-XCD mappings at the bench row counts (415, 196, 842 rows):
+// profiles/r07_lmhead_rows_plan_ab.txt — all within 1.5 %, this plan first or within 0.2 % of first at each.
+static GemmPlan plan_dyn(const ergm_gemm_desc* d) {
+    GemmPlan p;
+    const bool pipe = d->N % 8 == 0 && d->ldc % 8 == 0 && (d->k_count_dev || d->K % GEMM_BK == 0);
+    int split = 1;
+    if (!pipe) {
+        p.cfg = -1;
+        p.bm = p.bn = 64;
+    } else {
+        p.cfg = 2;
+        if (!d->k_count_dev && d->split_k != 1) split = std::max(1, std::min(16, d->K / 512));
+        int ocfg = -1, osplit = 1;
+        if (g_force_cfg >= 0 && dyn_cfg_ok(g_force_cfg)) {
+            p.cfg = g_force_cfg;
+            if (g_force_split > 0) split = g_force_split;
+        } else if (d->split_k == 0 && find_override(d, ocfg, osplit) && dyn_cfg_ok(ocfg)) {
+            p.cfg = ocfg;
+            split = osplit;
+        }
+        p.bm = kCfgs[p.cfg].bm;
+        p.bn = kCfgs[p.cfg].bn;
+        if (d->split_k > 1) split = d->split_k;
+        if (d->k_count_dev) split = 1;
+    }
+    const int kps = cdiv(cdiv(d->K, split), GEMM_BK) * GEMM_BK;
+    p.split = cdiv(d->K, kps);
+    p.kps = kps;
+    // a device-side row count with 8 or 16 K slices: slice = XCD (+ 8·blockIdx.z), see gemm_pipe_body
+    // (ERGM_DYN_XCD=0: tiles round the XCDs instead, for the A/B)
+    const char* e = getenv("ERGM_DYN_XCD");
+    p.xcd = p.cfg >= 0 && d->m_count_dev && p.split % 8 == 0 && (!e || atoi(e) != 0);
+    return p;
+}
+
+template <int C, bool AKM>
+static void launch_dyn_cfg(const GemmArgs& a, int split, hipStream_t s) {
+    constexpr PipeCfg c = kCfgs[C];
+    static_assert(dyn_cfg_ok(C) && c.np == 0 && c.ks == 1 && !c.direct && c.il == 0 && c.mf == 16, "plain pipelined cfg");
+    constexpr size_t lds = std::max((size_t)c.ns * (c.bm + c.bn) * GEMM_BK * 2, (size_t)(c.bm / c.wgm) * (c.bn + 4) * 4);
+    auto k = gemm_pipe_dyn_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, AKM, true>;
+    static bool attr = (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
+    (void)attr;
+    const dim3 grid = a.xcd_split ? dim3(8 * a.tiles_m * a.tiles_n, 1, split / 8) : dim3(a.tiles_m * a.tiles_n, 1, split);
+    ERGM_LAUNCH(k, grid, dim3(64 * c.wgm * c.wgn), lds, s, a);
+}
+
+template <bool AKM>
+static void launch_dyn(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+    switch (p.cfg) {
+        case 0: launch_dyn_cfg<0, AKM>(a, p.split, s); break;
+        case 2: launch_dyn_cfg<2, AKM>(a, p.split, s); break;
+        case 6: launch_dyn_cfg<6, AKM>(a, p.split, s); break;
+        case 14: launch_dyn_cfg<14, AKM>(a, p.split, s); break;
+        default: {  // register-staged 64x64 kernel: any K, N and leading dimensions
+            constexpr size_t lds = std::max((size_t)2 * (64 + 64) * GEMM_BK * 2, (size_t)64 * (64 + 4) * 4);
+            auto k = gemm_kernel<64, 64, AKM, true, ERGM_EPI_NONE, false, true>;
+            static bool attr = (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
+            (void)attr;
+            ERGM_LAUNCH(k, dim3(a.tiles_m * a.tiles_n, 1, p.split), dim3(GEMM_THREADS), lds, s, a);
+        }
+    }
+    if (p.split > 1) {
+        const size_t total = (size_t)a.M * a.N;
+        const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
+        ERGM_LAUNCH((splitk_reduce_kernel<ERGM_EPI_NONE, false, true>), dim3(blocks), dim3(256), 0, s, a, p.split);
+    }
+}
+
 }  // namespace ergm
 
 using namespace ergm;
@@ -1679,7 +1796,7 @@ extern "C" int ergm_gemm_tune(int cfg, int split) {
 
 extern "C" size_t ergm_gemm_workspace_size(const ergm_gemm_desc* d) {
     if (!d) return 0;
-    GemmPlan p = plan_gemm(d);
+    GemmPlan p = is_dyn(d) ? plan_dyn(d) : plan_gemm(d);  // device-side extents: sized for the capacities M, K
     if (p.split <= 1) return 0;
     return (size_t)p.split * d->M * d->N * sizeof(float) + (d->bias_grad ? (size_t)p.split * d->N * sizeof(float) : 0);
 }
@@ -1751,6 +1868,9 @@ static GemmArgs make_args(const ergm_gemm_desc* d, const void* A, const void* B,
     a.colsum = cs_in ? d->bias_grad : nullptr;
     a.colsum_part = nullptr;
     a.xcd_split = p.xcd && p.cfg >= 0 && kCfgs[p.cfg].np == 0 && kCfgs[p.cfg].ks == 1 && kCfgs[p.cfg].mf == 16 ? 1 : 0;
+    a.m_dev = d->m_count_dev;
+    a.k_dev = d->k_count_dev;
+    a.row_map = d->row_map;
     return a;
 }
 }  // namespace ergm
@@ -1787,6 +1907,9 @@ static int validate_desc(const ergm_gemm_desc* d, const void* A, const void* B, 
     ERGM_CHECK_ARG(!d->bias_grad || (d->a_layout == ERGM_KM && d->b_layout == ERGM_KN && e == ERGM_EPI_NONE &&
                                      d->c_dtype == ERGM_F32),
                    "ergm_gemm: bias_grad needs a_layout KM, b_layout KN, epilogue NONE and f32 C");
+    ERGM_CHECK_ARG(!(d->m_count_dev || d->k_count_dev || d->row_map) ||
+                       (d->b_layout == ERGM_KN && e == ERGM_EPI_NONE && d->c_dtype == ERGM_F32 && !d->bias_grad),
+                   "ergm_gemm: m_count_dev / k_count_dev / row_map need b_layout KN, epilogue NONE, f32 C, no bias_grad");
 
     return ERGM_OK;
 }
@@ -1797,10 +1920,23 @@ extern "C" int ergm_gemm(const ergm_gemm_desc* d, const void* A, const void* B, 
     ERGM_TRY(validate_desc(d, A, B, C));
     const int e = d->epilogue;
     trace_shape(d);
+    hipStream_t s = as_stream(stream);
+    if (is_dyn(d)) {
+        const GemmPlan p = plan_dyn(d);
+        GemmArgs a = make_args(d, A, B, C, p);
+        if (p.split > 1) {
+            const size_t need = (size_t)p.split * d->M * d->N * sizeof(float);
+            ERGM_CHECK_ARG(ws && ws_bytes >= need, "ergm_gemm: split-K %d needs %zu workspace bytes (got %zu)", p.split,
+                           need, ws_bytes);
+            a.slab = reinterpret_cast<float*>(ws);
+        }
+        if (d->a_layout == ERGM_KM) launch_dyn<true>(a, p, s);
+        else launch_dyn<false>(a, p, s);
+        return check_launch("ergm_gemm");
+    }
     GemmPlan p = plan_gemm(d);
     GemmArgs a = make_args(d, A, B, C, p);
     const bool cs_in = a.colsum != nullptr;
-    hipStream_t s = as_stream(stream);
     if (p.split > 1) {
         size_t need = (size_t)p.split * d->M * d->N * sizeof(float) + (d->bias_grad ? (size_t)p.split * d->N * 4 : 0);
         ERGM_CHECK_ARG(ws && ws_bytes >= need, "ergm_gemm: split-K %d needs %zu workspace bytes (got %zu)", p.split,

@@ -60,7 +60,10 @@ int loss_finalize_metrics(const float* row_loss, int T, const int* n_valid_globa
                           const float* emo_logits, const int64_t* emo_labels, int B, int C, hipStream_t s);
 int gemm_dw_pair(const ergm_gemm_desc* const d[2], const void* const A[2], const void* const B[2], void* const C[2],
                  void* stream, bool launch);
-int dlogits_add(void* dl, const void* g, const float* scale, size_t n, hipStream_t s);
+int dlogits_expand_add(void* dense, const void* dl_c, const int* pos, const void* g, const float* scale, int T, int ld,
+                       hipStream_t s);
+int gather_rows(const void* src, int ld_src, const int* rows, const int* counts, void* dst, int ld_dst, int cols, int cap,
+                hipStream_t s);
 int embed_fwd_ld(const int64_t* ids, const int64_t* tt, const int64_t* cap_ids, const float* wte, const float* wpe,
                  const float* vis, int ld_vis, const float* aud, float* h0, void* cap, int ld_cap, int B, int S, int E,
                  int V, hipStream_t s, const DropSite& drop);
@@ -117,7 +120,20 @@ struct ergm_model_plan {
     std::vector<LayerActs> la;
     __bf16 *cap, *kv_all, *lnf;
     float *mf, *rf;
+    // The LM loss scores only the rows whose next label is valid (the response turn), so the LM-head backward runs
+    // over those rows alone.  lm_rows[j] = the j-th scored logits row (ascending), lm_pos[t] = its index or -1,
+    // lm_cnt = {n, n rounded up to 64}: written on the side stream by every training forward (ergm_lm_rows), never
+    // read by the host in a normal step.  dlogits holds the n compact gradient rows (+ zero rows up to lm_cnt[1];
+    // capacity R64 = T rounded up to 64 rows), lnf_c the matching rows of lnf.  dlogits_dense: the T-row form, only
+    // for a caller's gradient on the logits (allocated when the first one arrives).
     __bf16* dlogits;
+    __bf16* lnf_c;
+    int *lm_rows, *lm_pos, *lm_cnt;
+    int R64;
+    __bf16* dlogits_dense = nullptr;
+    int* lm_cnt_host = nullptr;      // pinned copy of lm_cnt for the list probe's FLOP count (probed steps only)
+    hipEvent_t ev_lm_cnt = nullptr;  // ... and the event behind its copy
+    bool lm_cnt_copied = false;
     float *row_loss, *emo_sum, *emo_tmp;
     int* n_valid_local;
     // feature projections (feat_dim != n_embd): bf16 operands [2][Bp][Fd+8] (visual rows, then audio
@@ -286,7 +302,13 @@ size_t carve(ergm_model_plan* P, char* base) {
     P->kv_all = c.take<__bf16>(T * 2 * E * L);
     P->lnf = c.take<__bf16>(T * E);
     P->mf = c.take<float>(T); P->rf = c.take<float>(T);
-    P->dlogits = c.take<__bf16>(T * d.vocab_pad);
+    const size_t R64 = (T + 63) / 64 * 64;
+    P->R64 = (int)R64;
+    P->dlogits = c.take<__bf16>(R64 * d.vocab_pad);
+    P->lnf_c = c.take<__bf16>(R64 * E);
+    P->lm_rows = c.take<int>(T);
+    P->lm_pos = c.take<int>(T);
+    P->lm_cnt = c.take<int>(4);
     P->row_loss = c.take<float>(T);
     P->emo_sum = c.take<float>(4);
     P->emo_tmp = c.take<float>((size_t)d.batch * 16 + 8);
@@ -419,13 +441,15 @@ struct Probe {
 int gemm(ergm_model_plan* P, hipStream_t s, int M, int N, int K, const void* A, int lda, int al, const void* B,
          int ldb, int bl, void* C, int ldc, int cdt, int epi, const float* bias = nullptr, const void* aux = nullptr,
          int ld_aux = 0, void* aux_out = nullptr, int ld_aux_out = 0, const float* alpha_dev = nullptr,
-         const ergm_dropout* dropout = nullptr, float* bias_grad = nullptr) {
+         const ergm_dropout* dropout = nullptr, float* bias_grad = nullptr, const int* m_dev = nullptr,
+         const int* k_dev = nullptr, const int* row_map = nullptr) {
     ergm_gemm_desc g;
     memset(&g, 0, sizeof(g));
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.a_layout = al; g.b_layout = bl; g.c_dtype = cdt; g.epilogue = epi; g.alpha = 1.0f;
     g.bias = bias; g.aux = aux; g.ld_aux = ld_aux; g.aux_out = aux_out; g.ld_aux_out = ld_aux_out;
     g.split_k = 0; g.alpha_dev = alpha_dev; g.dropout = dropout; g.bias_grad = bias_grad;
+    g.m_count_dev = m_dev; g.k_count_dev = k_dev; g.row_map = row_map;
     size_t w = ergm_gemm_workspace_size(&g);
     ERGM_TRY(ws_need(P, w));
     if (P->dry) return ERGM_OK;
@@ -880,6 +904,9 @@ extern "C" int ergm_model_destroy(ergm_model_plan* P) {
         if (e) hipEventDestroy(e);
     if (P->ev_fork) hipEventDestroy(P->ev_fork);
     if (P->side) hipStreamDestroy(P->side);
+    if (P->ev_lm_cnt) hipEventDestroy(P->ev_lm_cnt);
+    if (P->lm_cnt_host) hipHostFree(P->lm_cnt_host);
+    if (P->dlogits_dense) hipFree(P->dlogits_dense);
     delete P;
     return ERGM_OK;
 }
@@ -909,6 +936,14 @@ extern "C" int ergm_model_set_probe_list(ergm_model_plan* P, int probe, void** e
 }
 
 extern "C" int ergm_model_probe_count(const ergm_model_plan* P) { return P ? P->evl_k : 0; }
+
+extern "C" int ergm_model_copy_head_dy(ergm_model_plan* P, float* dst, void* stream) {
+    ERGM_CHECK_ARG(P && dst, "model_copy_head_dy: null argument");
+    const size_t bytes = (size_t)P->T * P->d.n_embd * sizeof(float);
+    return hipMemcpyAsync(dst, P->dy, bytes, hipMemcpyDeviceToDevice, as_stream(stream)) == hipSuccess
+               ? ERGM_OK
+               : fail(ERGM_EHIP, "model_copy_head_dy: copy failed");
+}
 
 extern "C" int ergm_model_set_dropout(ergm_model_plan* P, float attn_p, float resid_p, float embd_p, uint64_t seed,
                                       uint32_t offset, int batch_base) {
@@ -1227,9 +1262,27 @@ int do_forward(ergm_model_plan* P, void* logits, float* emo_logits, float* out_l
     };
     // the side stream's tail of forward work: the embedding backward's sort (it needs only the ids: done here, off
     // the critical chain), then the mark
+    // ... and what the LM-head backward needs besides the logits: the list of scored rows (from the labels alone;
+    // no labels: an empty list) and P->dy zeroed — the LM-head dX writes only the scored rows, and dy is free from
+    // the previous step's ln_f backward (this stream forked from s above) until this step's head stage.  Their
+    // readers (the cross-entropy, the head stage) run on s behind the join of mark L.
     auto side_tail = [&]() -> int {
-        if (train && !P->dry)
+        if (train && !P->dry) {
             ERGM_TRY(embed_bwd_sort(P->ids, P->tt, P->cap_ids, T, d.vocab, P->keys, P->row_flag, d.vocab_pad, ss));
+            ERGM_TRY(ergm_lm_rows(P->labels, B, S, d.vocab, P->lm_rows, P->lm_pos, P->lm_cnt, ss));
+            if (hipMemsetAsync(P->dy, 0, (size_t)T * E * 4, ss) != hipSuccess) return fail(ERGM_EHIP, "memset");
+            P->lm_cnt_copied = false;
+            if (P->probe == 5 && P->evl_n > 0) {  // the list probe's steps record the FLOPs the LM-head dW issues
+                if (!P->lm_cnt_host && hipHostMalloc(reinterpret_cast<void**>(&P->lm_cnt_host), 2 * sizeof(int), 0) != hipSuccess)
+                    return fail(ERGM_EHIP, "model: pinned allocation failed");
+                if (!P->ev_lm_cnt && hipEventCreateWithFlags(&P->ev_lm_cnt, hipEventDisableTiming) != hipSuccess)
+                    return fail(ERGM_EHIP, "model: event creation failed");
+                if (hipMemcpyAsync(P->lm_cnt_host, P->lm_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, ss) != hipSuccess ||
+                    hipEventRecord(P->ev_lm_cnt, ss) != hipSuccess)
+                    return fail(ERGM_EHIP, "model: row count copy failed");
+                P->lm_cnt_copied = true;
+            }
+        }
         return side_mark(P, L);
     };
     const bool kvb = P->kv_per_block && !P->dry;
@@ -1296,11 +1349,13 @@ int do_forward(ergm_model_plan* P, void* logits, float* emo_logits, float* out_l
     if (P->dry) return ERGM_OK;
     ERGM_TRY(ergm_emotion_head(P->lnf, p.emo_w, P->emo_labels, emo_logits, P->emo_sum, nullptr, nullptr, P->emo_tmp,
                                B, S, E, 7, P->n_valid ? P->n_valid + 1 : nullptr, nullptr, s));
-    if (P->labels) {
-        ERGM_TRY(ergm_xent_fwd_bwd(logits, d.vocab_pad, P->labels, P->n_valid, P->row_loss, train ? P->dlogits : nullptr,
-                                   B, S, d.vocab, 1.0f, s));
-    } else if (train) {
-        ERGM_TRY(hipMemsetAsync(P->dlogits, 0, (size_t)T * d.vocab_pad * 2, s) == hipSuccess ? ERGM_OK : ERGM_EHIP);
+    if (P->labels && train) {  // the gradient rows of the scored positions only, at their index in the row list
+        ERGM_TRY(ergm_xent_compact(logits, d.vocab_pad, P->labels, P->n_valid, P->row_loss, P->dlogits, P->lm_pos,
+                                   P->lm_cnt, B, S, d.vocab, s));
+    } else if (P->labels) {
+        ERGM_TRY(ergm_xent_fwd_bwd(logits, d.vocab_pad, P->labels, P->n_valid, P->row_loss, nullptr, B, S, d.vocab, 1.0f,
+                                   s));
+    } else if (train) {  // no LM loss: the row list is empty, so the head stage reads no gradient row
         ERGM_TRY(hipMemsetAsync(P->row_loss, 0, (size_t)T * 4, s) == hipSuccess ? ERGM_OK : ERGM_EHIP);
     }
     if (P->labels || P->emo_labels) {
@@ -1357,26 +1412,56 @@ int do_backward_head(ergm_model_plan* P, const float* gscale, hipStream_t s) {
     // the lookup gradients into the same buffer).
     // a caller's gradient on the returned logits (src/model.py:698 returns differentiable logits): added to the
     // cross-entropy's dlogits, scaled by the loss gradient there, so the LM-head GEMMs run with alpha 1
+    // Default: both GEMMs run over the n scored rows only (the compact dlogits rows of the forward, n in device
+    // memory): dy[lm_rows[j]] = dlogits_c[j]·wte with every other row of dy left at the forward's zero fill, and
+    // dwte = dlogits_cᵀ·lnf_c contracted over lm_cnt[1] rows.  With a caller's gradient every row can be non-zero:
+    // the compact rows are expanded into a T-row buffer with the caller's added, and the dense GEMMs run on that.
     const float* lm_scale = gscale;
-    if (P->logits_grad && !P->dry) {
-        ERGM_TRY(dlogits_add(P->dlogits, P->logits_grad, gscale, (size_t)T * Vp, s));
+    const bool dense = P->logits_grad && !P->dry;
+    if (dense) {
+        if (!P->dlogits_dense &&
+            hipMalloc(reinterpret_cast<void**>(&P->dlogits_dense), (size_t)T * Vp * sizeof(__bf16)) != hipSuccess)
+            return fail(ERGM_EHIP, "model: allocation of the dense logits gradient (%zu bytes) failed", (size_t)T * Vp * 2);
+        ERGM_TRY(dlogits_expand_add(P->dlogits_dense, P->dlogits, P->lm_pos, P->logits_grad, gscale, T, Vp, s));
         lm_scale = nullptr;
     }
     P->logits_grad = nullptr;
+    static const int kDryCnt[2] = {0, 0};  // dry pass: any non-null pointer selects the plan sized for n = T
+    const int* cnt = P->dry ? kDryCnt : P->lm_cnt;
     auto lm_dw = [&]() -> int {
         ERGM_TRY(fork_side(P, s));
         hipStream_t ss = P->dry ? s : P->side;
-        Probe pr(P, 3, ss);
-        Probe pr5(P, 5, ss, 2.0 * Vp * E * T);
-        ERGM_TRY(gemm(P, ss, Vp, E, T, P->dlogits, Vp, ERGM_KM, P->lnf, E, ERGM_KN, p.g_wte, E, ERGM_F32,
-                      ERGM_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, lm_scale));
+        if (dense || P->dry) {
+            Probe pr(P, 3, ss);
+            Probe pr5(P, 5, ss, 2.0 * Vp * E * T);
+            ERGM_TRY(gemm(P, ss, Vp, E, T, P->dlogits_dense, Vp, ERGM_KM, P->lnf, E, ERGM_KN, p.g_wte, E, ERGM_F32,
+                          ERGM_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, lm_scale));
+        }
+        if (!dense) {
+            double flops = 2.0 * Vp * E * T;
+            if (!P->dry) {
+                ERGM_TRY(gather_rows(P->lnf, E, P->lm_rows, P->lm_cnt, P->lnf_c, E, E, P->R64, ss));
+                if (P->probe == 5 && P->evl_n > 0 && P->lm_cnt_copied) {  // probed steps: the FLOPs actually issued
+                    if (hipEventSynchronize(P->ev_lm_cnt) != hipSuccess) return fail(ERGM_EHIP, "model: event wait");
+                    flops = 2.0 * Vp * E * P->lm_cnt_host[1];
+                }
+            }
+            Probe pr(P, 3, ss);
+            Probe pr5(P, 5, ss, flops);
+            ERGM_TRY(gemm(P, ss, Vp, E, T, P->dlogits, Vp, ERGM_KM, P->lnf_c, E, ERGM_KN, p.g_wte, E, ERGM_F32,
+                          ERGM_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, lm_scale, nullptr, nullptr, nullptr, cnt + 1));
+        }
         return side_mark(P, L + 1);
     };
     if (P->lm_dw_first) ERGM_TRY(lm_dw());
     {
         Probe pr(P, 2, s);
-        ERGM_TRY(gemm(P, s, T, E, Vp, P->dlogits, Vp, ERGM_MK, p.wte_b, E, ERGM_KN, P->dy, E, ERGM_F32, ERGM_EPI_NONE,
-                      nullptr, nullptr, 0, nullptr, 0, lm_scale));
+        if (dense || P->dry)
+            ERGM_TRY(gemm(P, s, T, E, Vp, P->dlogits_dense, Vp, ERGM_MK, p.wte_b, E, ERGM_KN, P->dy, E, ERGM_F32,
+                          ERGM_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, lm_scale));
+        if (!dense)
+            ERGM_TRY(gemm(P, s, T, E, Vp, P->dlogits, Vp, ERGM_MK, p.wte_b, E, ERGM_KN, P->dy, E, ERGM_F32, ERGM_EPI_NONE,
+                          nullptr, nullptr, 0, nullptr, 0, lm_scale, nullptr, nullptr, cnt, nullptr, P->dry ? cnt : P->lm_rows));
     }
     if (!P->lm_dw_first) ERGM_TRY(lm_dw());
     if (P->dry) return ERGM_OK;

@@ -23,14 +23,33 @@ __device__ __forceinline__ void ms_combine(float& m, float& s, float m2, float s
 
 // Row in registers (NCH chunks of 8 bf16 per thread: a single HBM read), one fused block reduction
 // of the per-thread (max, Σexp) pairs, LSE, and dlogits = (softmax − onehot)/n_valid in the same pass.
-template <int NCH>
+// COMPACT: the gradient row of scored row t goes to row pos[t] of dlogits (the list of ergm_lm_rows; the same
+// arithmetic, so the row is bitwise the dense form's), an ignored row writes only its zero loss, and the 63
+// workgroups past the T rows write the zero rows counts[0] .. counts[1]-1 that pad the list to a whole K step of
+// the LM-head weight-gradient GEMM.
+template <int NCH, bool COMPACT = false>
 __global__ __launch_bounds__(XE_THREADS) void xent_kernel(const __bf16* __restrict__ logits, int ldl,
                                                           const int64_t* __restrict__ labels,
                                                           const int* __restrict__ n_valid, float* __restrict__ row_loss,
-                                                          __bf16* __restrict__ dlogits, int S, int V) {
+                                                          __bf16* __restrict__ dlogits, int S, int V, int T = 0,
+                                                          const int* __restrict__ pos = nullptr,
+                                                          const int* __restrict__ counts = nullptr) {
     __shared__ float red_m[XE_THREADS / 64], red_s[XE_THREADS / 64];
     __shared__ float tgt_logit;
     const int t = blockIdx.x;
+    if constexpr (COMPACT) {
+        if (t >= T) {
+            const int j = counts[0] + (t - T);
+            if (j < counts[1]) {
+                bf16x8 z;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) z[k] = f2bf(0.f);
+                for (int ch = threadIdx.x; ch * 8 < ldl; ch += XE_THREADS)
+                    *reinterpret_cast<bf16x8*>(dlogits + (size_t)j * ldl + ch * 8) = z;
+            }
+            return;
+        }
+    }
     const int b = t / S, s = t % S;
     long long target = -100;
     if (s < S - 1) target = labels[(size_t)b * S + s + 1];
@@ -38,7 +57,7 @@ __global__ __launch_bounds__(XE_THREADS) void xent_kernel(const __bf16* __restri
     const __bf16* row = logits + (size_t)t * ldl;
     if (!valid) {
         if (threadIdx.x == 0) row_loss[t] = 0.f;
-        if (dlogits) {
+        if (!COMPACT && dlogits) {
             bf16x8 z;
 #pragma unroll
             for (int j = 0; j < 8; ++j) z[j] = f2bf(0.f);
@@ -96,6 +115,7 @@ __global__ __launch_bounds__(XE_THREADS) void xent_kernel(const __bf16* __restri
     if (threadIdx.x == 0) row_loss[t] = lse - tgt_logit;
     if (!dlogits) return;
     const float inv_n = 1.0f / (float)max(1, *n_valid);
+    __bf16* drow = dlogits + (size_t)(COMPACT ? pos[t] : t) * ldl;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         const int ch = threadIdx.x + i * XE_THREADS;
@@ -108,9 +128,73 @@ __global__ __launch_bounds__(XE_THREADS) void xent_kernel(const __bf16* __restri
                 if (c < V) g = (__expf(bf2f(x[i][j]) - lse) - (c == target ? 1.f : 0.f)) * inv_n;
                 d[j] = f2bf(g);
             }
-            *reinterpret_cast<bf16x8*>(dlogits + (size_t)t * ldl + ch * 8) = d;
+            *reinterpret_cast<bf16x8*>(drow + ch * 8) = d;
         }
     }
+}
+
+// The scored rows of the LM loss, in ascending order: rows[j] = t of the j-th row t = b·S+s with s < S-1 and
+// 0 <= labels[b][s+1] < V (xent_kernel's predicate), rows[j] = -1 for n <= j < T; pos[t] = j or -1;
+// counts[0] = n, counts[1] = n rounded up to GEMM K steps of 64.  One workgroup, an exclusive prefix sum over
+// 1024-row chunks with a running base: the same list in every run, any T.  labels == nullptr: no row is scored.
+constexpr int ROWS_THREADS = 1024;
+__global__ __launch_bounds__(ROWS_THREADS) void lm_rows_kernel(const int64_t* __restrict__ labels, int T, int S, int V,
+                                                               int* __restrict__ rows, int* __restrict__ pos,
+                                                               int* __restrict__ counts) {
+    __shared__ int wsum[ROWS_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int base = 0;
+    for (int t0 = 0; t0 < T; t0 += ROWS_THREADS) {
+        const int t = t0 + threadIdx.x;
+        int f = 0;
+        if (labels && t < T && t % S < S - 1) {
+            const int64_t y = labels[t + 1];
+            f = y >= 0 && y < V;
+        }
+        int x = f;  // inclusive scan over the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wsum[wave] = x;
+        __syncthreads();
+        int woff = 0, tot = 0;
+#pragma unroll
+        for (int w = 0; w < ROWS_THREADS / 64; ++w) {
+            const int v = wsum[w];
+            if (w < wave) woff += v;
+            tot += v;
+        }
+        const int j = base + woff + x - f;
+        if (t < T) {
+            pos[t] = f ? j : -1;
+            if (f) rows[j] = t;
+        }
+        base += tot;
+        __syncthreads();
+    }
+    for (int j = base + threadIdx.x; j < T; j += ROWS_THREADS) rows[j] = -1;
+    if (threadIdx.x == 0) {
+        counts[0] = base;
+        counts[1] = (base + 63) / 64 * 64;
+    }
+}
+
+// dst[j] = src[rows[j]] for j < counts[0], zeros for counts[0] <= j < counts[1] (bf16 rows of `cols` columns, 8 per
+// thread): the ln_f rows of the scored positions, the B operand of the compact LM-head weight-gradient GEMM.
+__global__ __launch_bounds__(128) void gather_rows_kernel(const __bf16* __restrict__ src, int ld_src,
+                                                          const int* __restrict__ rows, const int* __restrict__ counts,
+                                                          __bf16* __restrict__ dst, int ld_dst, int cols) {
+    const int j = blockIdx.x;
+    if (j >= counts[1]) return;
+    const int t = j < counts[0] ? rows[j] : -1;
+    bf16x8 z;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) z[k] = f2bf(0.f);
+    for (int c = threadIdx.x * 8; c < cols; c += 128 * 8)
+        *reinterpret_cast<bf16x8*>(dst + (size_t)j * ld_dst + c) =
+            t >= 0 ? *reinterpret_cast<const bf16x8*>(src + (size_t)t * ld_src + c) : z;
 }
 
 // counts[0] = LM rows the CE scores (label at s >= 1 scores logits row s-1; valid iff 0 <= y < V, the
@@ -337,12 +421,47 @@ extern "C" int ergm_xent_fwd_bwd(const void* logits, int ldl, const int64_t* lab
     auto* dl = reinterpret_cast<__bf16*>(dlogits);
     hipStream_t s = as_stream(stream);
     dim3 grid(B * S), blk(XE_THREADS);
-    if (nch <= 2) ERGM_LAUNCH(xent_kernel<2>, grid, blk, 0, s, lg, ldl, labels, n_valid_global, row_loss, dl, S, V);
-    else if (nch <= 4) ERGM_LAUNCH(xent_kernel<4>, grid, blk, 0, s, lg, ldl, labels, n_valid_global, row_loss, dl, S, V);
-    else if (nch <= 8) ERGM_LAUNCH(xent_kernel<8>, grid, blk, 0, s, lg, ldl, labels, n_valid_global, row_loss, dl, S, V);
-    else if (nch <= 13) ERGM_LAUNCH(xent_kernel<13>, grid, blk, 0, s, lg, ldl, labels, n_valid_global, row_loss, dl, S, V);
-    else ERGM_LAUNCH(xent_kernel<16>, grid, blk, 0, s, lg, ldl, labels, n_valid_global, row_loss, dl, S, V);
+    if (nch <= 2) ERGM_LAUNCH(xent_kernel<2>, grid, blk, 0, s, lg, ldl, labels, n_valid_global, row_loss, dl, S, V, 0,
+                       (const int*)nullptr, (const int*)nullptr);
+    else if (nch <= 4) ERGM_LAUNCH(xent_kernel<4>, grid, blk, 0, s, lg, ldl, labels, n_valid_global, row_loss, dl, S, V, 0,
+                       (const int*)nullptr, (const int*)nullptr);
+    else if (nch <= 8) ERGM_LAUNCH(xent_kernel<8>, grid, blk, 0, s, lg, ldl, labels, n_valid_global, row_loss, dl, S, V, 0,
+                       (const int*)nullptr, (const int*)nullptr);
+    else if (nch <= 13) ERGM_LAUNCH(xent_kernel<13>, grid, blk, 0, s, lg, ldl, labels, n_valid_global, row_loss, dl, S, V, 0,
+                       (const int*)nullptr, (const int*)nullptr);
+    else ERGM_LAUNCH(xent_kernel<16>, grid, blk, 0, s, lg, ldl, labels, n_valid_global, row_loss, dl, S, V, 0,
+                       (const int*)nullptr, (const int*)nullptr);
     return check_launch("xent");
+}
+
+extern "C" int ergm_lm_rows(const int64_t* labels, int B, int S, int V, int* rows, int* pos, int* counts, void* stream) {
+    ERGM_CHECK_ARG(rows && pos && counts && B > 0 && S > 0 && V > 0, "lm_rows: bad argument");
+    ERGM_CHECK_ARG((long long)B * S < (1LL << 30), "lm_rows: too many rows");
+    ERGM_LAUNCH(lm_rows_kernel, dim3(1), dim3(ROWS_THREADS), 0, as_stream(stream), labels, B * S, S, V, rows, pos, counts);
+    return check_launch("lm_rows");
+}
+
+extern "C" int ergm_xent_compact(const void* logits, int ldl, const int64_t* labels, const int* n_valid_global,
+                                 float* row_loss, void* dlogits_c, const int* pos, const int* counts, int B, int S, int V,
+                                 void* stream) {
+    ERGM_CHECK_ARG(logits && labels && n_valid_global && row_loss && dlogits_c && pos && counts, "xent_compact: null argument");
+    ERGM_CHECK_ARG(B > 0 && S > 0 && V > 0 && ldl >= V && ldl % 8 == 0, "xent_compact: bad shape (ldl %% 8 == 0 required)");
+    ERGM_CHECK_ARG(aligned16(logits) && aligned16(dlogits_c), "xent_compact: 16-byte alignment");
+    const int nch = cdiv(cdiv(ldl, 8), XE_THREADS);
+    ERGM_CHECK_ARG(nch <= XE_MAXCH, "xent_compact: row of %d columns too long", ldl);
+    const auto* lg = reinterpret_cast<const __bf16*>(logits);
+    auto* dl = reinterpret_cast<__bf16*>(dlogits_c);
+    hipStream_t s = as_stream(stream);
+    const int T = B * S;
+    dim3 grid(T + 63), blk(XE_THREADS);  // the last 63 workgroups write the zero pad rows
+#define ERGM_XE_C(N) ERGM_LAUNCH((xent_kernel<N, true>), grid, blk, 0, s, lg, ldl, labels, n_valid_global, row_loss, dl, S, V, T, pos, counts)
+    if (nch <= 2) ERGM_XE_C(2);
+    else if (nch <= 4) ERGM_XE_C(4);
+    else if (nch <= 8) ERGM_XE_C(8);
+    else if (nch <= 13) ERGM_XE_C(13);
+    else ERGM_XE_C(16);
+#undef ERGM_XE_C
+    return check_launch("xent_compact");
 }
 
 extern "C" int ergm_emotion_head(const void* h, const float* W, const int64_t* labels, float* logits, float* loss_sum,
@@ -373,26 +492,44 @@ extern "C" int ergm_loss_finalize(const float* row_loss, int T, const int* n_val
 }
 
 namespace ergm {
-// dl[i] = bf16(scale · dl[i] + g[i]) over n bf16 elements (8 per thread): a caller's gradient on the returned
-// logits added to the cross-entropy's, both scaled as the LM-head backward GEMMs expect (alpha 1).
-__global__ __launch_bounds__(256) void dlogits_add_kernel(bf16x8* __restrict__ dl, const bf16x8* __restrict__ g,
-                                                          const float* __restrict__ scale, size_t n8) {
+// dense[t] = bf16(scale · (pos[t] >= 0 ? dl_c[pos[t]] : 0) + g[t]) over T rows of ld bf16 columns (8 per thread): a
+// caller's gradient on the returned logits added to the cross-entropy's compact rows, both scaled as the LM-head
+// backward GEMMs expect (alpha 1).  The value the dense form gave: an ignored row's cross-entropy gradient is 0.
+__global__ __launch_bounds__(256) void dlogits_expand_add_kernel(bf16x8* __restrict__ dense,
+                                                                 const bf16x8* __restrict__ dl_c,
+                                                                 const int* __restrict__ pos, const bf16x8* __restrict__ g,
+                                                                 const float* __restrict__ scale, size_t n8, int ld8) {
     const float sc = scale ? *scale : 1.0f;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
-        bf16x8 a = dl[i];
+        const size_t t = i / ld8, c = i % ld8;
+        const int j = pos[t];
+        bf16x8 a;
+        if (j >= 0) a = dl_c[(size_t)j * ld8 + c];
         const bf16x8 b = g[i];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = f2bf(sc * bf2f(a[j]) + bf2f(b[j]));
-        dl[i] = a;
+        for (int k = 0; k < 8; ++k) a[k] = f2bf(sc * (j >= 0 ? bf2f(a[k]) : 0.f) + bf2f(b[k]));
+        dense[i] = a;
     }
 }
-int dlogits_add(void* dl, const void* g, const float* scale, size_t n, hipStream_t s) {
-    ERGM_CHECK_ARG(dl && g && n % 8 == 0 && aligned16(dl) && aligned16(g), "dlogits_add: bad argument");
-    const size_t n8 = n / 8;
+int dlogits_expand_add(void* dense, const void* dl_c, const int* pos, const void* g, const float* scale, int T, int ld,
+                       hipStream_t s) {
+    ERGM_CHECK_ARG(dense && dl_c && pos && g && ld % 8 == 0 && aligned16(dense) && aligned16(dl_c) && aligned16(g),
+                   "dlogits_expand_add: bad argument");
+    const size_t n8 = (size_t)T * (ld / 8);
     const unsigned grid = (unsigned)std::min<size_t>((n8 + 255) / 256, 4096);
-    ERGM_LAUNCH(dlogits_add_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<bf16x8*>(dl),
-                       reinterpret_cast<const bf16x8*>(g), scale, n8);
-    return check_launch("dlogits_add");
+    ERGM_LAUNCH(dlogits_expand_add_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<bf16x8*>(dense),
+                       reinterpret_cast<const bf16x8*>(dl_c), pos, reinterpret_cast<const bf16x8*>(g), scale, n8, ld / 8);
+    return check_launch("dlogits_expand_add");
+}
+
+// dst[j] = src[rows[j]] (j < counts[0]), zero rows up to counts[1]; `cap` = the row capacity of dst (the grid).
+int gather_rows(const void* src, int ld_src, const int* rows, const int* counts, void* dst, int ld_dst, int cols, int cap,
+                hipStream_t s) {
+    ERGM_CHECK_ARG(src && rows && counts && dst && cols % 8 == 0 && ld_src % 8 == 0 && ld_dst % 8 == 0 && cap > 0 &&
+                       aligned16(src) && aligned16(dst), "gather_rows: bad argument");
+    ERGM_LAUNCH(gather_rows_kernel, dim3(cap), dim3(128), 0, s, reinterpret_cast<const __bf16*>(src), ld_src, rows, counts,
+                       reinterpret_cast<__bf16*>(dst), ld_dst, cols);
+    return check_launch("gather_rows");
 }
 
 // ergm_loss_finalize that also accumulates the trainer metrics (ergm_model_set_metrics).

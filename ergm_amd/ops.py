@@ -33,9 +33,13 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, a_layout: int
          out: Optional[torch.Tensor] = None, out_dtype=torch.float32, epilogue: int = L.EPI_NONE,
          bias: Optional[torch.Tensor] = None, aux: Optional[torch.Tensor] = None,
          aux_out: Optional[torch.Tensor] = None, alpha: float = 1.0, split_k: int = 0,
-         alpha_dev: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+         alpha_dev: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
+         m_count: Optional[torch.Tensor] = None, k_count: Optional[torch.Tensor] = None,
+         row_map: Optional[torch.Tensor] = None) -> torch.Tensor:
     """C[M,N] = epilogue(alpha · A·B); A/B bf16 row-major with layouts as in ergm_hip.h.  ``bias_grad`` (f32 [N],
-    KM x KN weight gradients only) also receives alpha·Σ_k B[k][n]."""
+    KM x KN weight gradients only) also receives alpha·Σ_k B[k][n].  ``m_count`` / ``k_count`` (device int32
+    scalars) and ``row_map`` (device int32 [M]) are the device-side extents and the store's row map of
+    ergm_gemm_desc: M and K are then capacities, and rows of ``out`` no computed row maps to are left as they are."""
     _need_gpu(A, B)
     assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16
     lda = A.stride(0) if A.dim() == 2 else (K if a_layout == L.MK else M)
@@ -46,7 +50,10 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, a_layout: int
                    c_dtype=L.BF16 if out.dtype == torch.bfloat16 else L.F32, epilogue=epilogue, alpha=alpha,
                    bias=_ptr(bias), aux=_ptr(aux), ld_aux=aux.stride(0) if aux is not None else 0,
                    aux_out=_ptr(aux_out), ld_aux_out=aux_out.stride(0) if aux_out is not None else 0,
-                   split_k=split_k, alpha_dev=_ptr(alpha_dev), bias_grad=_ptr(bias_grad))
+                   split_k=split_k, alpha_dev=_ptr(alpha_dev), bias_grad=_ptr(bias_grad), m_count_dev=_ptr(m_count),
+                   k_count_dev=_ptr(k_count), row_map=_ptr(row_map))
+    for t in (m_count, k_count, row_map):
+        assert t is None or (t.is_cuda and t.dtype == torch.int32)
     lib = L.load()
     wsb = lib.ergm_gemm_workspace_size(C.byref(d))
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=A.device)
@@ -343,6 +350,31 @@ def xent(logits, labels, n_valid, V, with_grad=True):
     L.call("ergm_xent_fwd_bwd", _ptr(logits), logits.stride(0), _ptr(labels), _ptr(n_valid), _ptr(rl), _ptr(dl), B, S, V,
            1.0, _stream(logits.device))
     return rl, dl
+
+
+def lm_rows(labels, V):
+    """The rows the LM loss scores (ergm_lm_rows): (rows int32 [B*S], pos int32 [B*S], counts int32 [2] = n, n
+    rounded up to 64), all on the device."""
+    B, S = labels.shape
+    dev = labels.device
+    rows = torch.empty(B * S, dtype=torch.int32, device=dev)
+    pos = torch.empty(B * S, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    L.call("ergm_lm_rows", _ptr(labels), B, S, V, _ptr(rows), _ptr(pos), _ptr(counts), _stream(dev))
+    return rows, pos, counts
+
+
+def xent_compact(logits, labels, n_valid, V, pos, counts, out=None):
+    """ergm_xent_compact: (row_loss [B*S], dlogits_c [B*S rounded up to 64, ldl]) with the gradient row of scored
+    row t at row pos[t] and zero rows from counts[0] to counts[1]; the other rows of ``out`` are left as they are."""
+    B, S = labels.shape
+    rl = torch.empty(B * S, dtype=torch.float32, device=logits.device)
+    if out is None:
+        out = torch.empty((B * S + 63) // 64 * 64, logits.stride(0), dtype=torch.bfloat16, device=logits.device)
+    assert out.shape[0] >= (B * S + 63) // 64 * 64 and out.stride(0) == logits.stride(0)
+    L.call("ergm_xent_compact", _ptr(logits), logits.stride(0), _ptr(labels), _ptr(n_valid), _ptr(rl), _ptr(out),
+           _ptr(pos), _ptr(counts), B, S, V, _stream(logits.device))
+    return rl, out
 
 
 def emotion_head(h, W, labels, B, S, n_valid=None, dh=None, grad_scale=None):

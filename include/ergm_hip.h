@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define ERGM_ABI_VERSION 11  /* 11: ergm_dp_sum_adamw takes max_blocks */
+#define ERGM_ABI_VERSION 12  /* 12: ergm_gemm_desc device-side extents + row map, ergm_lm_rows, ergm_xent_compact */
 
 typedef enum {
     ERGM_OK = 0,
@@ -124,6 +124,18 @@ typedef struct {
                           * also write alpha·Σ_k B[k][n] (the Conv1D bias gradient, column sums of dY over
                           * the K tokens) to bias_grad[n], f32 [N]; NULL = none.  Computed from the B
                           * fragments the GEMM already stages (no second pass over dY), deterministic. */
+    /* Extents in device memory (ABI 12; all NULL by default; b_layout KN, epilogue NONE, f32 C, no bias_grad).  M
+     * and K are then capacities: the grid and the split-K workspace are sized for them on the host, and the
+     * kernels read the extents when they run (nothing waits inside a kernel).
+     *   m_count_dev  int*: only rows m < min(M, *m_count_dev) are computed and stored; a tile whose first row lies
+     *                past the count returns at once.  Rows of A at or past the count are never used.
+     *   k_count_dev  int*: the contraction runs over k < *k_count_dev, a multiple of 64 no larger than K rounded
+     *                up to 64 (A and B must hold that many k rows/columns); 0 writes C = 0.  Never split.
+     *   row_map      int[M]: computed row m is stored to row row_map[m] of C (rows of C no row maps to are not
+     *                written).  Entries at or past the row count are not read.                                */
+    const int* m_count_dev;
+    const int* k_count_dev;
+    const int* row_map;
 } ergm_gemm_desc;
 
 /* Tuning hook (calling thread only): force pipelined-kernel configuration `cfg` (tile / wave grid /
@@ -268,6 +280,17 @@ int ergm_count_valid(const int64_t* labels, const int64_t* emotion_labels, int B
                      int* counts, void* stream);
 int ergm_xent_fwd_bwd(const void* logits, int ldl, const int64_t* labels, const int* n_valid_global,
                       float* row_loss, void* dlogits, int B, int S, int V, float grad_scale,
+                      void* stream);
+/* The rows the LM loss scores, for an LM-head backward over those rows only (ABI 12).  ergm_lm_rows writes, from
+ * the labels alone (NULL: no row), rows[j] = the j-th row t = b*S+s with s < S-1 and 0 <= labels[b][s+1] < V in
+ * ascending order (rows[j] = -1 for n <= j < B*S), pos[t] = j or -1, counts[0] = n (the local count) and
+ * counts[1] = n rounded up to 64: a prefix sum in one workgroup, the same list in every run.
+ * ergm_xent_compact is ergm_xent_fwd_bwd (grad_scale 1) writing the gradient row of scored row t to row pos[t] of
+ * dlogits_c (bitwise the dense row), nothing for an ignored row (row_loss[t] = 0 as before), and zeros to rows
+ * counts[0] .. counts[1]-1; dlogits_c holds B*S rounded up to 64 rows of ldl bf16.                       */
+int ergm_lm_rows(const int64_t* labels, int B, int S, int V, int* rows, int* pos, int* counts, void* stream);
+int ergm_xent_compact(const void* logits, int ldl, const int64_t* labels, const int* n_valid_global,
+                      float* row_loss, void* dlogits_c, const int* pos, const int* counts, int B, int S, int V,
                       void* stream);
 /* Emotion head on the last token: logits[b][c] = Σ_e h[b,S-1,e]·W[c][e] (h bf16, W f32 [C][E]);
  * with labels: loss_sum = Σ_b CE_b over valid labels (0 <= y < C; others, e.g. -100, are ignored),
@@ -498,9 +521,14 @@ int ergm_model_set_probe(ergm_model_plan* plan, int probe, void* ev_begin, void*
  * in the following steps, up to n, and flops[k] (host array, may be NULL) receives its algorithmic FLOPs;
  * ergm_model_probe_count returns how many were recorded.  probe 5 = the weight-gradient GEMMs (every block's
  * Conv1D dW + bias, the stacked caption K/V dW, the LM-head dW), 6 = the block forward Conv1D GEMMs.
- * n = 0 disables. */
+ * n = 0 disables.  The LM-head dW runs over the scored rows only: in steps with list probe 5 active its entry is
+ * the FLOPs issued, 2·vocab_pad·n_embd·(scored rows rounded up to 64), from a host copy of the row count that
+ * only those steps make. */
 int ergm_model_set_probe_list(ergm_model_plan* plan, int probe, void** ev_begin, void** ev_end, double* flops, int n);
 int ergm_model_probe_count(const ergm_model_plan* plan);
+/* Copies the head stage's data gradient dy [batch*seq][n_embd] f32 (the LM-head dX plus the emotion head's rows
+ * seq-1) to dst on `stream`: valid between ergm_model_backward_head and the next training forward (ABI 12). */
+int ergm_model_copy_head_dy(ergm_model_plan* plan, float* dst, void* stream);
 
 /* Library information and errors. */
 int ergm_version(void);
