@@ -1,0 +1,444 @@
+// Batched KV-cache generation for gfx950: decode attention of one query per sequence over a ragged cache,
+// the embedding of one token per sequence at its own position, and nucleus (top-p) sampling of a batch of
+// logit rows without a sort (ergm_hip.h: ergm_attn_decode, ergm_embed_rows, ergm_topp_sample).
+//
+// Decode attention is a GEMV over the cache: VALU work behind 16-byte loads, no MFMA.  A workgroup of 4 waves
+// owns one (split, head, sequence).  8 lanes share a key row (8 bf16 of the 64-wide head each), so one wave
+// load covers 8 rows and a workgroup 32 rows per step, 4 steps in flight.  Each of the 32 key slots keeps
+// its own online softmax (m, l, o[8 per lane]); the slots are merged in slot order in LDS, the splits of one
+// (sequence, head) in split order by a second kernel, and the appended row is added last, from the qkv row
+// itself.  No float atomics anywhere: the output does not depend on scheduling.
+//
+// Sampling works on integers.  e_i = expf(x_i - max) is quantised to q_i = floor(e_i·2^30); every sum (the
+// softmax denominator, the mass above a threshold, the running sums of the draw) is a sum of those integers,
+// so LDS integer atomics and any reduction order give the same result, and the kept set is exactly the rule
+// of ergm_hip.h applied to the q_i.  The threshold (the smallest kept value) is found by a three-level
+// histogram over the bit pattern of e_i (monotone for positive floats): 11 + 11 + 9 bits, each level refining
+// the bin in which the mass above crosses top_p.
+#include "common.h"
+
+#include <algorithm>
+
+namespace ergm {
+
+constexpr int DEC_SLOTS = 32;       // key slots of a workgroup: 4 waves x 8 rows per wave load
+constexpr int DEC_DEPTH = 4;        // rows per slot loaded before the first is used (8 measured no faster)
+constexpr int DEC_MAX_SPLITS = 32;
+constexpr int DEC_PART = 66;        // floats of one split's partial: m, l, o[64]
+
+__device__ __forceinline__ void bf8_to_f32(const uint4& r, float* f) {
+    f[0] = __uint_as_float(r.x << 16); f[1] = __uint_as_float(r.x & 0xffff0000u);
+    f[2] = __uint_as_float(r.y << 16); f[3] = __uint_as_float(r.y & 0xffff0000u);
+    f[4] = __uint_as_float(r.z << 16); f[5] = __uint_as_float(r.z & 0xffff0000u);
+    f[6] = __uint_as_float(r.w << 16); f[7] = __uint_as_float(r.w & 0xffff0000u);
+}
+
+// Last stage, one full wave, lane d = head dimension d: (M, L, O) is the merged state over the cache rows.
+// With `append` the new row joins from the qkv row (never read back from the cache), then O / L is stored.
+__device__ __forceinline__ void decode_finish(float M, float Lsum, float O, int d, const __bf16* qrow, int E, bool append,
+                                              __bf16* out) {
+    if (append) {
+        const float s = wave_sum(bf2f(qrow[d]) * bf2f(qrow[E + d])) * 0.125f;
+        const float Mn = fmaxf(M, s);
+        const float c = M == -INFINITY ? 0.f : expf(M - Mn);
+        const float p = expf(s - Mn);
+        Lsum = Lsum * c + p;
+        O = O * c + p * bf2f(qrow[2 * E + d]);
+    }
+    out[d] = f2bf(Lsum > 0.f ? O / Lsum : 0.f);
+}
+
+__global__ __launch_bounds__(256) void attn_decode_kernel(const __bf16* __restrict__ qkv, int ld_qkv, __bf16* kc, __bf16* vc,
+                                                          int64_t ld_seq, int ld_row, const int* __restrict__ lens,
+                                                          int max_len, int append, int E, int splits,
+                                                          float* __restrict__ ws, __bf16* __restrict__ out, int ldo) {
+    __shared__ __attribute__((aligned(16))) float sm_o[DEC_SLOTS][64];
+    __shared__ float sm_m[DEC_SLOTS], sm_l[DEC_SLOTS];
+    const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, slot = lane >> 3, part = lane & 7;
+    const int n = max(0, min(lens[b], max_len - append));  // rows attended; the appended row goes to row n < max_len
+    const __bf16* qrow = qkv + (size_t)b * ld_qkv + 64 * h;
+    __bf16* kb = kc + (int64_t)b * ld_seq + 64 * h + 8 * part;
+    __bf16* vb = vc + (int64_t)b * ld_seq + 64 * h + 8 * part;
+    if (append && split == 0 && threadIdx.x < 16) {  // the new K | V row of this head, bitwise
+        const int which = threadIdx.x >> 3;
+        const uint4 r = *reinterpret_cast<const uint4*>(qrow + (1 + which) * E + 8 * part);
+        *reinterpret_cast<uint4*>((which ? vb : kb) + (int64_t)n * ld_row) = r;
+    }
+    // keys [k0, k1) of this split: equal chunks of a multiple of 32 rows, the last ones possibly empty
+    const int chunk = (int)((((int64_t)n + splits - 1) / splits + 31) & ~(int64_t)31);
+    const int k0 = (int)min((int64_t)n, (int64_t)split * chunk), k1 = min(n, k0 + chunk);
+    float q[8];
+    bf8_to_f32(*reinterpret_cast<const uint4*>(qrow + 8 * part), q);
+    float m = -INFINITY, l = 0.f, acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+    for (int base = k0; base < k1; base += DEC_DEPTH * DEC_SLOTS) {
+        uint4 kr[DEC_DEPTH], vr[DEC_DEPTH];
+#pragma unroll
+        for (int u = 0; u < DEC_DEPTH; ++u) {
+            const int t = base + u * DEC_SLOTS + wave * 8 + slot;
+            kr[u] = vr[u] = make_uint4(0, 0, 0, 0);
+            if (t < k1) {
+                kr[u] = *reinterpret_cast<const uint4*>(kb + (int64_t)t * ld_row);
+                vr[u] = *reinterpret_cast<const uint4*>(vb + (int64_t)t * ld_row);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < DEC_DEPTH; ++u) {
+            const int t = base + u * DEC_SLOTS + wave * 8 + slot;
+            float kf[8], vf[8];
+            bf8_to_f32(kr[u], kf);
+            bf8_to_f32(vr[u], vf);
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) s += q[i] * kf[i];
+            s += __shfl_xor(s, 1, 64);  // the 8 lanes of a row end with the same sum
+            s += __shfl_xor(s, 2, 64);
+            s += __shfl_xor(s, 4, 64);
+            s *= 0.125f;
+            if (t < k1) {
+                const float mn = fmaxf(m, s);
+                const float c = m == -INFINITY ? 0.f : expf(m - mn);
+                const float p = expf(s - mn);
+                l = l * c + p;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) acc[i] = acc[i] * c + p * vf[i];
+                m = mn;
+            }
+        }
+    }
+    const int sl = wave * 8 + slot;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sm_o[sl][8 * part + i] = acc[i];
+    if (part == 0) {
+        sm_m[sl] = m;
+        sm_l[sl] = l;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    float M = -INFINITY;
+    for (int j = 0; j < DEC_SLOTS; ++j) M = fmaxf(M, sm_m[j]);
+    float Lsum = 0.f, O = 0.f;
+    for (int j = 0; j < DEC_SLOTS; ++j) {  // slot order
+        const float w = sm_m[j] == -INFINITY ? 0.f : expf(sm_m[j] - M);
+        Lsum += sm_l[j] * w;
+        O += sm_o[j][lane] * w;
+    }
+    if (splits == 1) {
+        decode_finish(M, Lsum, O, lane, qrow, E, append != 0, out + (size_t)b * ldo + 64 * h);
+    } else {
+        float* p = ws + ((size_t)(b * gridDim.y + h) * splits + split) * DEC_PART;
+        if (lane == 0) {
+            p[0] = M;
+            p[1] = Lsum;
+        }
+        p[2 + lane] = O;
+    }
+}
+
+// splits > 1: merge the partials of one (sequence, head) in split order, then the appended row.
+__global__ __launch_bounds__(64) void attn_decode_merge_kernel(const __bf16* __restrict__ qkv, int ld_qkv,
+                                                               const float* __restrict__ ws, int splits, int append, int E,
+                                                               __bf16* __restrict__ out, int ldo) {
+    const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+    const float* p = ws + (size_t)(b * gridDim.x + h) * splits * DEC_PART;
+    // lane s holds split s's (m, l) and its weight; the o rows are independent loads, summed in split order
+    const float ms = lane < splits ? p[lane * DEC_PART] : -INFINITY;
+    const float ls = lane < splits ? p[lane * DEC_PART + 1] : 0.f;
+    const float M = wave_max(ms);
+    const float w = ms == -INFINITY ? 0.f : expf(ms - M);
+    float Lsum = 0.f, O = 0.f;
+#pragma unroll 8
+    for (int s = 0; s < splits; ++s) {
+        const float ws_ = __shfl(w, s, 64);
+        Lsum += __shfl(ls, s, 64) * ws_;
+        O += p[s * DEC_PART + 2 + lane] * ws_;
+    }
+    decode_finish(M, Lsum, O, lane, qkv + (size_t)b * ld_qkv + 64 * h, E, append != 0, out + (size_t)b * ldo + 64 * h);
+}
+
+// Workgroups for the 256 CUs, while every split keeps at least 256 rows of the longest possible cache: measured at
+// B·H = 12, a 1,024-row cache takes 15.7 us unsplit and 7.2 + 4 us (merge launch) in 4 splits, a 128-row cache 5.2 us
+// however it is split (profiles/r08_attn_decode_splits.txt), so shorter chunks only add the merge.
+static int decode_split_cap(int max_len) { return std::min(DEC_MAX_SPLITS, std::max(1, max_len / 256)); }
+static int decode_auto_splits(int B, int H, int max_len) {
+    const int cap = decode_split_cap(max_len);
+    const int64_t bh = (int64_t)B * H;
+    return (int)std::min<int64_t>(cap, std::max<int64_t>(1, (256 + bh - 1) / bh));
+}
+
+// ---- embedding of one token per sequence -----------------------------------------------------------
+__global__ __launch_bounds__(256) void embed_rows_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ tt,
+                                                         const int* __restrict__ pos, const float* __restrict__ wte,
+                                                         const float* __restrict__ wpe, float* __restrict__ h, int E, int V,
+                                                         int n_positions) {
+    const int b = blockIdx.x;
+    const int64_t id = min(max(ids[b], (int64_t)0), (int64_t)V - 1);
+    const int64_t ty = tt ? tt[b] : -1;
+    const int p = min(max(pos[b], 0), n_positions - 1);
+    const bool ok_ty = ty >= 0 && ty < V;
+    for (int c = threadIdx.x * 4; c < E; c += 1024) {  // ergm_embed_fwd's order: (wte[id] + wpe[p]) + wte[tt]
+        float4 x = *reinterpret_cast<const float4*>(wte + (size_t)id * E + c);
+        const float4 w = *reinterpret_cast<const float4*>(wpe + (size_t)p * E + c);
+        x.x += w.x; x.y += w.y; x.z += w.z; x.w += w.w;
+        if (ok_ty) {
+            const float4 y = *reinterpret_cast<const float4*>(wte + (size_t)ty * E + c);
+            x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
+        }
+        *reinterpret_cast<float4*>(h + (size_t)b * E + c) = x;
+    }
+}
+
+// ---- nucleus sampling --------------------------------------------------------------------------------
+constexpr int TP_THREADS = 1024;
+constexpr int TP_BINS = 2048;
+constexpr int TP_CNT_SHIFT = 47;  // a histogram word: count << 47 | mass (mass <= 53,248 · 2^30 < 2^46)
+constexpr unsigned long long TP_MASS_MASK = (1ull << TP_CNT_SHIFT) - 1;
+
+struct TpShared {
+    unsigned long long hist[TP_BINS];
+    unsigned long long scan[TP_THREADS];
+    unsigned long long pick[2];
+    float red[TP_THREADS / 64];
+    int sel;
+};
+
+// Exclusive prefix sum over the 1,024 threads in thread order (Hillis-Steele in LDS); `total` = the sum.
+__device__ __forceinline__ unsigned long long tp_scan(unsigned long long v, unsigned long long* buf,
+                                                      unsigned long long& total) {
+    const int t = threadIdx.x;
+    buf[t] = v;
+    __syncthreads();
+    for (int off = 1; off < TP_THREADS; off <<= 1) {
+        const unsigned long long a = t >= off ? buf[t - off] : 0ull;
+        __syncthreads();
+        buf[t] += a;
+        __syncthreads();
+    }
+    total = buf[TP_THREADS - 1];
+    const unsigned long long incl = buf[t];
+    __syncthreads();
+    return incl - v;
+}
+
+// e < 0 marks a slot that holds no token (past V, or a NaN logit): no mass, never counted
+__device__ __forceinline__ unsigned long long tp_q(float e) { return (unsigned long long)(fmaxf(e, 0.f) * 1073741824.f); }
+// The row lives in registers across several unrolled passes; an opaque copy per use keeps the compiler from
+// carrying each pass's derived values (64-bit masses, predicates) along with it, which spills.
+__device__ __forceinline__ float tp_use(float e) {
+    asm volatile("" : "+v"(e));
+    return e;
+}
+
+// One workgroup per row; thread t holds the `per` consecutive tokens from t·per in registers.
+template <int NPT>
+__global__ __launch_bounds__(TP_THREADS) void topp_sample_kernel(const float* __restrict__ logits, int ldl, int V,
+                                                                 float top_p, uint32_t seed_lo, uint32_t seed_hi,
+                                                                 uint32_t step, uint8_t* finished, int64_t eos_id,
+                                                                 int64_t* __restrict__ tokens, int* __restrict__ kept,
+                                                                 float* __restrict__ kept_mass) {
+    __shared__ TpShared sm;
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (finished && finished[b]) {  // uniform over the workgroup
+        if (t == 0) {
+            tokens[b] = eos_id;
+            if (kept) kept[b] = 0;
+            if (kept_mass) kept_mass[b] = 0.f;
+        }
+        return;
+    }
+    const int per = (V + TP_THREADS - 1) / TP_THREADS;
+    const int i0 = t * per;
+    const int nv = max(0, min(per, V - i0));  // valid tokens of this thread: j < nv
+    const float* row = logits + (size_t)b * ldl;
+    float e[NPT];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        e[j] = j < nv ? row[i0 + j] : -INFINITY;
+        mx = fmaxf(mx, e[j]);
+    }
+    mx = wave_max(mx);
+    if ((t & 63) == 0) sm.red[t >> 6] = mx;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < TP_THREADS / 64; ++w) mx = fmaxf(mx, sm.red[w]);
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const float x = expf(e[j] - mx);
+        e[j] = (j < nv && x >= 0.f) ? x : -1.f;
+        mine += tp_q(e[j]);
+    }
+    unsigned long long S;
+    tp_scan(mine, sm.scan, S);
+    // T: the largest mass of the ranks before a kept token
+    unsigned long long T = top_p >= 1.f ? S : (top_p <= 0.f ? 0ull : (unsigned long long)((double)top_p * (double)S));
+    T = min(T, S);
+    // threshold search: after level p, `prefix` = the leading bits of the smallest kept value, `above` = count
+    // and mass (packed) of the tokens whose value lies above every value with that prefix
+    unsigned prefix = 0;
+    unsigned long long above = 0, in_bin = 0;
+#pragma unroll 1
+    for (int level = 0; level < 3; ++level) {
+        const int shift = level == 0 ? 20 : (level == 1 ? 9 : 0);
+        const int bits = level == 2 ? 9 : 11;
+        sm.hist[t] = 0;
+        sm.hist[t + TP_THREADS] = 0;
+        if (t == 0) sm.sel = TP_BINS;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) {
+            const float ej = tp_use(e[j]);
+            const unsigned key = __float_as_uint(ej);
+            if (ej >= 0.f && (level == 0 || (key >> (shift + bits)) == prefix))
+                atomicAdd(&sm.hist[(key >> shift) & ((1u << bits) - 1)], (1ull << TP_CNT_SHIFT) | tp_q(ej));
+        }
+        __syncthreads();
+        // thread t owns bins bh > bl, the threads walk the bins downwards: an exclusive scan gives what lies above
+        const int bh = TP_BINS - 1 - 2 * t, bl = bh - 1;
+        const unsigned long long hh = sm.hist[bh], hl = sm.hist[bl];
+        unsigned long long tot;
+        const unsigned long long ah = above + tp_scan(hh + hl, sm.scan, tot), al = ah + hh;
+        // the smallest non-empty bin whose top value still has at most T above it holds the threshold
+        if (hl && (al & TP_MASS_MASK) <= T) atomicMin(&sm.sel, bl);
+        else if (hh && (ah & TP_MASS_MASK) <= T) atomicMin(&sm.sel, bh);
+        __syncthreads();
+        const int sel = sm.sel;
+        if (sel == bh || sel == bl) {
+            sm.pick[0] = sel == bh ? ah : al;
+            sm.pick[1] = sel == bh ? hh : hl;
+        }
+        __syncthreads();
+        above = sm.pick[0];
+        in_bin = sm.pick[1];
+        prefix = (prefix << bits) | (unsigned)sel;
+        __syncthreads();
+    }
+    // prefix = the bit pattern of the smallest kept value v; `in_bin` counts its ties, kept in token order while
+    // the mass before each stays <= T
+    const unsigned vkey = prefix;
+    const unsigned long long G = above & TP_MASS_MASK, qv = tp_q(__uint_as_float(vkey));
+    const unsigned ties = (unsigned)(in_bin >> TP_CNT_SHIFT);
+    const unsigned keep_ties = qv == 0 ? ties : (unsigned)min((unsigned long long)ties, (T - G) / qv + 1);
+    unsigned long long c_eq = 0;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) c_eq += __float_as_uint(tp_use(e[j])) == vkey ? 1u : 0u;
+    unsigned long long tot;
+    unsigned rank = (unsigned)tp_scan(c_eq, sm.scan, tot);  // ties in lower token ids
+    unsigned keepbits_lo = 0, keepbits_hi = 0;
+    mine = 0;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const float ej = tp_use(e[j]);
+        const unsigned key = __float_as_uint(ej);
+        bool k = ej >= 0.f && key > vkey;
+        if (key == vkey) k = rank++ < keep_ties;
+        if (k) {
+            mine += tp_q(ej);
+            if (j < 32) keepbits_lo |= 1u << j;
+            else keepbits_hi |= 1u << (j - 32);
+        }
+    }
+    unsigned long long K;
+    unsigned long long run = tp_scan(mine, sm.scan, K);
+    // the draw: first kept token, in token order, whose running sum reaches u·K
+    const uint4 r = philox4x32_10(make_uint4((uint32_t)b, 0u, 0xE5A3u, step), seed_lo, seed_hi);
+    const double u = ((double)r.x + 0.5) * (1.0 / 4294967296.0);
+    unsigned long long target = (unsigned long long)ceil(u * (double)K);
+    target = max(1ull, min(target, K));
+    if (t == 0) sm.sel = V - 1;
+    __syncthreads();
+    bool found = false;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const bool k = j < 32 ? (keepbits_lo >> j) & 1u : (keepbits_hi >> (j - 32)) & 1u;
+        if (k) {
+            run += tp_q(tp_use(e[j]));
+            if (!found && run >= target) {
+                found = true;
+                atomicMin(&sm.sel, i0 + j);
+            }
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        const int tok = sm.sel;
+        tokens[b] = tok;
+        if (kept) kept[b] = (int)(above >> TP_CNT_SHIFT) + (int)keep_ties;
+        if (kept_mass) kept_mass[b] = (float)((double)K / (double)S);
+        if (finished && tok == eos_id) finished[b] = 1;
+    }
+}
+
+}  // namespace ergm
+
+using namespace ergm;
+
+extern "C" size_t ergm_attn_decode_workspace_size(int B, int H, int max_len) {
+    if (B <= 0 || H <= 0 || max_len <= 0) return 0;
+    return (size_t)B * H * decode_split_cap(max_len) * DEC_PART * sizeof(float);
+}
+
+extern "C" int ergm_attn_decode(const void* qkv, int ld_qkv, void* kcache, void* vcache, int64_t ld_seq, int ld_row,
+                                const int* lens, int B, int H, int max_len, int append, int splits, void* out, int ldo,
+                                void* workspace, size_t ws_bytes, void* stream) {
+    ERGM_CHECK_ARG(qkv && kcache && vcache && lens && out, "attn_decode: null argument");
+    ERGM_CHECK_ARG(B > 0 && H > 0 && max_len > 0 && B <= 65535 && H <= 65535, "attn_decode: bad shape B %d H %d max_len %d",
+                   B, H, max_len);
+    ERGM_CHECK_ARG(append == 0 || append == 1, "attn_decode: append is 0 or 1");
+    const int E = 64 * H;
+    ERGM_CHECK_ARG(ld_qkv % 8 == 0 && ld_row % 8 == 0 && ld_seq % 8 == 0 && ldo % 8 == 0,
+                   "attn_decode: strides must be multiples of 8 elements");
+    ERGM_CHECK_ARG(ld_qkv >= (append ? 3 * E : E) && ld_row >= E && ldo >= E &&
+                       ld_seq >= (int64_t)(max_len - 1) * ld_row + E,
+                   "attn_decode: stride shorter than the rows it spans");
+    ERGM_CHECK_ARG(aligned16(qkv) && aligned16(kcache) && aligned16(vcache) && aligned16(out),
+                   "attn_decode: 16-byte alignment");
+    ERGM_CHECK_ARG(splits >= 0 && splits <= DEC_MAX_SPLITS, "attn_decode: splits %d outside [0, %d]", splits,
+                   DEC_MAX_SPLITS);
+    if (splits == 0) splits = decode_auto_splits(B, H, max_len);
+    ERGM_CHECK_ARG(splits == 1 || (workspace && ws_bytes >= (size_t)B * H * splits * DEC_PART * sizeof(float)),
+                   "attn_decode: workspace too small for %d splits", splits);
+    hipStream_t s = as_stream(stream);
+    auto* q = reinterpret_cast<const __bf16*>(qkv);
+    auto* o = reinterpret_cast<__bf16*>(out);
+    ERGM_LAUNCH(attn_decode_kernel, dim3(splits, H, B), dim3(256), 0, s, q, ld_qkv, reinterpret_cast<__bf16*>(kcache),
+                reinterpret_cast<__bf16*>(vcache), ld_seq, ld_row, lens, max_len, append, E, splits,
+                reinterpret_cast<float*>(workspace), o, ldo);
+    if (splits > 1)
+        ERGM_LAUNCH(attn_decode_merge_kernel, dim3(H, B), dim3(64), 0, s, q, ld_qkv,
+                    reinterpret_cast<const float*>(workspace), splits, append, E, o, ldo);
+    return check_launch("attn_decode");
+}
+
+extern "C" int ergm_embed_rows(const int64_t* ids, const int64_t* tt, const int* pos, const float* wte, const float* wpe,
+                               float* h, int B, int E, int V, int n_positions, void* stream) {
+    ERGM_CHECK_ARG(ids && pos && wte && wpe && h, "embed_rows: null argument");
+    ERGM_CHECK_ARG(B > 0 && E > 0 && E % 4 == 0 && V > 0 && n_positions > 0, "embed_rows: bad shape");
+    ERGM_CHECK_ARG(aligned16(wte) && aligned16(wpe) && aligned16(h), "embed_rows: 16-byte alignment");
+    ERGM_LAUNCH(embed_rows_kernel, dim3(B), dim3(256), 0, as_stream(stream), ids, tt, pos, wte, wpe, h, E, V, n_positions);
+    return check_launch("embed_rows");
+}
+
+extern "C" int ergm_topp_sample(const float* logits, int ldl, int B, int V, float top_p, uint64_t seed, uint32_t step,
+                                void* finished, int64_t eos_id, int64_t* tokens, int* kept, float* kept_mass,
+                                void* stream) {
+    ERGM_CHECK_ARG(logits && tokens, "topp_sample: null argument");
+    ERGM_CHECK_ARG(B > 0 && V > 0 && ldl >= V, "topp_sample: bad shape B %d V %d ldl %d", B, V, ldl);
+    ERGM_CHECK_ARG(top_p == top_p, "topp_sample: top_p is NaN");
+    if (V > 52 * TP_THREADS) return fail(ERGM_EUNSUPPORTED, "topp_sample: V %d > %d", V, 52 * TP_THREADS);
+    hipStream_t s = as_stream(stream);
+    auto* fin = reinterpret_cast<uint8_t*>(finished);
+    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
+    const int per = cdiv(V, TP_THREADS);
+#define ERGM_TOPP(NPT)                                                                                              \
+    ERGM_LAUNCH(topp_sample_kernel<NPT>, dim3(B), dim3(TP_THREADS), 0, s, logits, ldl, V, top_p, lo, hi, step, fin, \
+                eos_id, tokens, kept, kept_mass)
+    if (per <= 4) ERGM_TOPP(4);
+    else if (per <= 16) ERGM_TOPP(16);
+    else ERGM_TOPP(52);
+#undef ERGM_TOPP
+    return check_launch("topp_sample");
+}

@@ -300,6 +300,64 @@ def embed_fwd(ids, tt, cap_ids, wte, wpe, vis=None, aud=None, dropout: Optional[
     return h0, cap
 
 
+def attn_decode_workspace(B: int, H: int, max_len: int, device, splits: int = 0) -> torch.Tensor:
+    """The fp32 workspace ergm_attn_decode needs for the automatic split count (or for a forced ``splits``)."""
+    n = max(L.load().ergm_attn_decode_workspace_size(B, H, max_len), B * H * max(splits, 1) * 66 * 4, 16)
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def attn_decode(qkv, kcache, vcache, lens, append: bool, splits: int = 0, out=None, ws=None):
+    """One query per sequence over a ragged cache (ergm_attn_decode).  qkv [B, >= E (3E with ``append``)] bf16;
+    kcache / vcache: [B, max_len, E] bf16 views (any sequence and row strides) of the per-sequence K and V rows;
+    lens int32 [B] on the device.  With ``append`` the new K/V row is stored at row lens[b] and attended too."""
+    _need_gpu(qkv, kcache, vcache, lens)
+    assert qkv.dtype == kcache.dtype == vcache.dtype == torch.bfloat16 and lens.dtype == torch.int32
+    B, max_len, E = kcache.shape
+    if vcache.shape != kcache.shape or vcache.stride() != kcache.stride() or kcache.stride(2) != 1 or E % 64:
+        raise ValueError("attn_decode: kcache / vcache must be [B, max_len, 64·H] views with the same strides")
+    if qkv.shape[0] != B or lens.numel() != B or qkv.stride(1) != 1:
+        raise ValueError("attn_decode: qkv and lens must have one row per sequence")
+    H = E // 64
+    dev = qkv.device
+    if out is None:
+        out = torch.empty(B, E, dtype=torch.bfloat16, device=dev)
+    if ws is None and splits != 1:
+        ws = attn_decode_workspace(B, H, max_len, dev, splits)
+    L.call("ergm_attn_decode", _ptr(qkv), qkv.stride(0), _ptr(kcache), _ptr(vcache), kcache.stride(0), kcache.stride(1),
+           _ptr(lens), B, H, max_len, int(bool(append)), splits, _ptr(out), out.stride(0), _ptr(ws),
+           0 if ws is None else ws.numel() * ws.element_size(), _stream(dev))
+    return out
+
+
+def embed_rows(ids, tt, pos, wte, wpe, out=None):
+    """h[b] = wte[ids[b]] + wpe[pos[b]] + wte[tt[b]] (ergm_embed_rows): ids / tt int64 [B], pos int32 [B]."""
+    _need_gpu(ids, pos, wte, wpe)
+    assert ids.dtype == torch.int64 and pos.dtype == torch.int32 and (tt is None or tt.dtype == torch.int64)
+    B = ids.numel()
+    V, E = wte.shape
+    if out is None:
+        out = torch.empty(B, E, dtype=torch.float32, device=ids.device)
+    L.call("ergm_embed_rows", _ptr(ids), _ptr(tt), _ptr(pos), _ptr(wte), _ptr(wpe), _ptr(out), B, E, V, wpe.shape[0],
+           _stream(ids.device))
+    return out
+
+
+def topp_sample(logits, V: int, top_p: float, seed: int, step: int, eos_id: int, finished=None, tokens=None,
+                kept=None, kept_mass=None):
+    """Nucleus sampling of the rows of logits [B, >= V] f32 on the device (ergm_topp_sample); returns ``tokens``
+    (int64 [B]).  ``finished`` (uint8 [B]) is read and updated; ``kept`` (int32 [B]) / ``kept_mass`` (f32 [B]) are
+    optional diagnostics."""
+    _need_gpu(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    assert finished is None or finished.dtype == torch.uint8
+    B = logits.shape[0]
+    if tokens is None:
+        tokens = torch.empty(B, dtype=torch.int64, device=logits.device)
+    L.call("ergm_topp_sample", _ptr(logits), logits.stride(0), B, V, float(top_p), seed & (2 ** 64 - 1),
+           step & 0xFFFFFFFF, _ptr(finished), eos_id, _ptr(tokens), _ptr(kept), _ptr(kept_mass), _stream(logits.device))
+    return tokens
+
+
 def feat_pool(x: torch.Tensor, lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """Mean over frames of encoder outputs x [B, T, D] (f32 / bf16, any row strides with unit
     last-dim stride) -> [B, D] f32; ``lengths`` [B] int32 limits each sample to its valid frames.

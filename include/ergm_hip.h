@@ -23,6 +23,8 @@
  *   ergm_xent_fwd_bwd     CrossEntropyLoss(ignore_index=-100) on shifted logits (src/model.py:704-708)
  *   ergm_emotion_head     emotion_head + its CrossEntropyLoss (src/model.py:700-701,710-711)
  *   ergm_adamw_step       torch.optim.AdamW.step (src/main.py:68,155)
+ *   ergm_attn_decode, ergm_embed_rows, ergm_topp_sample
+ *                         the per-token work of nucleus_sampling (src/main.py:253-282), for a batch
  *   ergm_model_*          the whole GPT2LMHeadModel.forward (src/model.py:654-737) and its
  *                         backward (src/main.py:154) as one native launch sequence
  */
@@ -36,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ERGM_ABI_VERSION 12  /* 12: ergm_gemm_desc device-side extents + row map, ergm_lm_rows, ergm_xent_compact */
+#define ERGM_ABI_VERSION 13  /* 13: ergm_attn_decode, ergm_embed_rows, ergm_topp_sample (batched generation) */
 
 typedef enum {
     ERGM_OK = 0,
@@ -227,6 +229,25 @@ int ergm_attn_bwd(const void* q, const void* k, const void* v, const void* o, co
  * tiled kernels' LDS ring depth (0 = per-kernel defaults; 2, 3 or 4).  Process-wide; not for concurrent use with
  * running attention calls. */
 int ergm_attn_tune(int force_generic);
+/* Decode attention (ABI 13; generation, src/main.py:253-282): one query per sequence over a ragged K/V cache.  For
+ * b < B, h < H (head_dim 64, scale 1/8, bf16 in, f32 math, bf16 out):
+ *   n_b = clamp(lens[b], 0, max_len - append)         (lens: device int [B], read when the kernel runs, never written)
+ *   q = qkv[b][64h .. 64h+64)                          (qkv [B][ld_qkv] bf16)
+ *   cache row t of sequence b at kcache / vcache + b*ld_seq + t*ld_row, head h at columns [64h, 64h+64); K and V
+ *   may interleave in one [max_len][2E] buffer (vcache = kcache + E, ld_row = 2E).
+ * append = 0 (cross-attention): out[b] = softmax(q·Kᵀ/8)·V over rows t < n_b of a read-only cache; n_b = 0 writes zeros.
+ * append = 1 (self-attention): the new key qkv[b][E + 64h ..) and value qkv[b][2E + 64h ..) are stored, bitwise, to
+ * row n_b, and the query attends rows 0 .. n_b, the new row taken from qkv (no workgroup reads another's store).
+ * No cache row at or past max_len and no sequence at or past B is read or written, whatever lens holds.
+ * splits: the rows t < n_b are cut into `splits` chunks of ceil(n_b / splits) rounded up to 32 rows, one workgroup
+ * per (chunk, head, sequence); with splits > 1 the partials (m, l, o[64]: 66 floats per chunk) go through
+ * `workspace` (B*H*splits*66 floats) and are merged in chunk order.  0 = automatic (1 when B*H fills the chip),
+ * at most 32; ergm_attn_decode_workspace_size covers the automatic choice.  No float atomics: the same inputs give
+ * the same bits in every run.  Every stride is a multiple of 8 elements, every pointer 16-byte aligned.        */
+size_t ergm_attn_decode_workspace_size(int B, int H, int max_len);
+int ergm_attn_decode(const void* qkv, int ld_qkv, void* kcache, void* vcache, int64_t ld_seq, int ld_row,
+                     const int* lens, int B, int H, int max_len, int append, int splits, void* out, int ldo,
+                     void* workspace, size_t ws_bytes, void* stream);
 
 /* LayerNorm over rows of E (biased variance, eps): y(bf16) = (x-μ)·rstd·γ + β; x f32.        */
 int ergm_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, float* mean,
@@ -254,6 +275,25 @@ int ergm_colsum(const void* X, int x_dtype, int rows, int cols, int ldx, float* 
 int ergm_embed_fwd(const int64_t* ids, const int64_t* tt, const int64_t* cap_ids, const float* wte,
                    const float* wpe, const float* vis, int ld_vis, const float* aud, float* h0,
                    void* cap, int B, int S, int E, int V, const ergm_dropout* dropout, void* stream);
+/* One token per sequence at its own position (ABI 13; a decode step of B ragged sequences):
+ *   h[b] = (wte[ids[b]] + wpe[clamp(pos[b], 0, n_positions-1)]) + wte[tt[b]]            (f32 [B][E])
+ * in ergm_embed_fwd's summation order: a row equals that kernel's row for the same token at the same position
+ * (positions >= 2, or no features).  pos: device int [B] (the cache lengths).  ids outside [0, V) are clamped, a
+ * tt outside it adds nothing (as ergm_embed_fwd), tt may be NULL: no index is ever followed out of a table. */
+int ergm_embed_rows(const int64_t* ids, const int64_t* tt, const int* pos, const float* wte, const float* wpe,
+                    float* h, int B, int E, int V, int n_positions, void* stream);
+/* Nucleus sampling of B logit rows (ABI 13; src/main.py:259-270 without the sort and without a host round trip).
+ * logits f32 [B][ldl], the first V columns count (V <= 53,248).  p = softmax(row); rank the tokens by descending p,
+ * ties by ascending token id; the token of rank r is kept iff r == 0 or the summed p of the ranks < r is <= top_p
+ * (the reference's `cumsum > top_p` shifted right by one).  The draw: u = (w + 0.5) / 2^32 with w = word 0 of
+ * Philox4x32-10(counter {b, 0, 0xE5A3, step}, key seed); the token is the first kept token, in ascending token id,
+ * whose running sum of kept p reaches u · (the kept mass): the reference's renormalised multinomial in distribution.
+ * Arithmetic: e = expf(x - max) in f32, then every sum over the integers floor(e · 2^30), so no result depends on a
+ * summation order.  finished (uint8 [B], in/out, may be NULL): a row with a nonzero flag emits eos_id and draws
+ * nothing; a row that draws eos_id sets its flag.  tokens int64 [B]; kept (int [B]) and kept_mass (f32 [B], the
+ * kept share of the row's probability) are optional outputs, 0 for a finished row.                          */
+int ergm_topp_sample(const float* logits, int ldl, int B, int V, float top_p, uint64_t seed, uint32_t step,
+                     void* finished, int64_t eos_id, int64_t* tokens, int* kept, float* kept_mass, void* stream);
 /* Feature pooling (data_process/feature_extraction.py:63,69: torch.mean(last_hidden_state, dim=1) of the
  * wav2vec2 / BLIP-vision encoder outputs): out[b][d] = mean_{t < len_b} x[b][t][d], x f32 or bf16 with
  * strides ld_t (frames) and ld_b (samples) in elements, lengths optional (NULL = all T frames; padded

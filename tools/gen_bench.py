@@ -1,0 +1,120 @@
+"""Generation throughput and decode-attention bandwidth (recorded in DESIGN.md, not gated by any test).
+
+Workload: GPT-2-small (random weights, so the nucleus is most of the vocabulary), prompt 64, captions 64, 64 new
+tokens, top_p 0.95, an eos id no token has (every sequence runs to the bound).  tokens/s = B·64 over the time of the
+whole call (prefill + sampling + decode), HIP events around it, 1 warm-up and the median of 5 repeats, for
+  kv       KVCacheGenerator.nucleus_sampling, one sequence (the baseline)
+  b1/8/32  BatchedGenerator.generate at B = 1, 8, 32
+and ``attn``: ergm_attn_decode (append = 0, H = 12) at cache lengths 128 and 1,024 for B = 1 and 32, bytes/s = the
+K/V bytes of the attended rows over the mean time of 200 back-to-back launches (median of 5 such windows), the
+caches rotated through enough buffers to exceed the 256 MiB Infinity Cache where memory allows; set against the
+6.3 TB/s an HBM copy reaches.  A window of back-to-back launches includes the launch gaps and the host's enqueue rate
+(about 12-15 us per call from Python): for the kernel's own time run one shape under the profiler, in a run of its own,
+  rocprofv3 --kernel-trace --stats -d OUT -- python tools/gen_bench.py --case attn --shape 32,1024
+and divide the same byte count by the mean duration of attn_decode_kernel (plus attn_decode_merge_kernel when the
+automatic split is above 1).
+
+Without --case the tool runs every case in turn, each in a fresh child process under its own timeout, one at a
+time, and stops at the first that fails.  Usage (GPU box): python tools/gen_bench.py [--case kv|b1|b8|b32|attn]"""
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+CASES = {"kv": 240, "b1": 240, "b8": 240, "b32": 240, "attn": 240}  # seconds each child may take
+PROMPT = CAPS = NEW = 64
+TOP_P, NO_EOS, SP2 = 0.95, -1, 50259
+REPEATS = 5
+
+
+def _event_ms(fn):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def _generation(case):
+    import torch
+    from ergm_amd.config import ERGMConfig, NO_DROPOUT
+    from ergm_amd.generate import BatchedGenerator, KVCacheGenerator
+    from ergm_amd.model import GPT2LMHeadModel
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = GPT2LMHeadModel(ERGMConfig(**NO_DROPOUT), device=dev)
+    B = 1 if case == "kv" else int(case[1:])
+    g = torch.Generator().manual_seed(1)
+    prompts = [(torch.randint(0, 50000, (1, PROMPT), generator=g).to(dev), torch.full((1, PROMPT), SP2, device=dev),
+                torch.randint(0, 50000, (1, CAPS), generator=g).to(dev), None, None) for _ in range(B)]
+    if case == "kv":
+        def run():
+            gen = KVCacheGenerator(model, max_len=PROMPT + NEW)
+            out = gen.nucleus_sampling(*prompts[0][:3], top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2,
+                                       generator=torch.Generator(device=dev).manual_seed(7))
+            assert len(out) == NEW
+    else:
+        gen = BatchedGenerator(model, max_batch=B, max_len=PROMPT + NEW)
+
+        def run():
+            out = gen.generate(prompts, top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2, seed=7, max_new_tokens=NEW)
+            assert all(len(r) == NEW for r in out)
+    run()  # warm-up: code objects, GEMM plans, allocator
+    ms = [_event_ms(run) for _ in range(REPEATS)]
+    med = statistics.median(ms)
+    print(json.dumps({"case": case, "B": B, "new_tokens": NEW, "ms_median": round(med, 2),
+                      "ms_all": [round(x, 2) for x in ms], "tokens_per_s": round(B * NEW / med * 1e3, 1)}), flush=True)
+
+
+def _attention():
+    import torch
+    from ergm_amd import ops
+    dev = torch.device("cuda:0")
+    H, E, N = 12, 768, 200
+    only = sys.argv[sys.argv.index("--shape") + 1].split(",") if "--shape" in sys.argv else None
+    for B in (1, 32):
+        for n in (128, 1024):
+            if only and [str(B), str(n)] != only:
+                continue
+            nbytes = B * n * 2 * E * 2
+            nbuf = max(1, min(8, -(-(512 << 20) // nbytes)))
+            caches = [torch.randn(B, n, 2 * E, device=dev).bfloat16() for _ in range(nbuf)]
+            q = torch.randn(B, E, device=dev).bfloat16()
+            lens = torch.full((B,), n, dtype=torch.int32, device=dev)
+            ws = ops.attn_decode_workspace(B, H, n, dev)
+            out = torch.empty(B, E, dtype=torch.bfloat16, device=dev)
+
+            def window():
+                for i in range(N):
+                    c = caches[i % nbuf]
+                    ops.attn_decode(q, c[:, :, :E], c[:, :, E:], lens, False, out=out, ws=ws)
+            window()
+            us = statistics.median(_event_ms(window) for _ in range(REPEATS)) / N * 1e3
+            print(json.dumps({"case": "attn", "B": B, "cache_len": n, "kv_bytes": nbytes, "buffers": nbuf,
+                              "us_per_launch": round(us, 2), "TB_per_s": round(nbytes / us / 1e6, 3),
+                              "share_of_6.3TBps": round(nbytes / us / 1e6 / 6.3, 3)}), flush=True)
+
+
+def main():
+    if "--case" in sys.argv:
+        case = sys.argv[sys.argv.index("--case") + 1]
+        if case not in CASES:
+            raise SystemExit(f"unknown case {case}")
+        _attention() if case == "attn" else _generation(case)
+        return
+    for case, limit in CASES.items():
+        try:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", case], timeout=limit)
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"case {case} exceeded {limit} s: stopping")
+        if r.returncode != 0:
+            raise SystemExit(f"case {case} failed with status {r.returncode}: stopping")
+
+
+if __name__ == "__main__":
+    main()
