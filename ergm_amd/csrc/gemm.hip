@@ -14,8 +14,10 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "tiles.h"
@@ -1094,6 +1096,20 @@ struct PipeCfg {
     int il = 0;      // 1: next-stage DMA pieces interleaved with the step's reads / MFMAs (gemm_pipe_body IL)
     int ks = 1;      // 2: intra-workgroup split-K over two wave groups (gemm_ks2_body; ns counts K-step pairs)
     int mf = 16;     // 32: v_mfma_f32_32x32x16_bf16 on 32x32 fragments (gemm_pipe_body MF; pipelined kernel only)
+
+    // What a configuration is and can do: every user (make_args, plan_dyn, the launchers, gemm_dw_pair) asks here.
+    enum Family { PIPE, WS, KS2 };  // gemm_pipe_kernel / gemm_ws_kernel / gemm_ks2_kernel
+    constexpr Family family() const { return ks == 2 ? KS2 : np > 0 ? WS : PIPE; }
+    constexpr int threads() const { return 64 * (wgm * wgn * ks + np); }
+    constexpr size_t lds_bytes() const {  // the operand ring, or the epilogue's staging rows of one wave row
+        return std::max((size_t)ns * ks * (bm + bn) * GEMM_BK * 2, (size_t)(bm / wgm) * (bn + 4) * 4);
+    }
+    // the in-kernel bias column sums (GemmArgs::colsum); the other kernels get the column-sum pass
+    constexpr bool has_colsum() const { return family() == PIPE && mf == 16; }
+    // one K slice per XCD (GemmArgs::xcd_split)
+    constexpr bool xcd_ok() const { return family() == PIPE && mf == 16; }
+    // gemm_pipe_kernel with none of its variants: what gemm_pipe_dyn_kernel is
+    constexpr bool plain() const { return family() == PIPE && !direct && il == 0 && mf == 16; }
 };
 static constexpr PipeCfg kCfgs[] = {
     {64, 64, 2, 2, 4},     // 0
@@ -1151,6 +1167,50 @@ static constexpr PipeCfg kCfgs[] = {
 };
 static constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 
+static constexpr bool has_colsum(int c) { return kCfgs[c].has_colsum(); }
+// The configurations instantiated for device-side extents (gemm_pipe_dyn_kernel) ...
+static constexpr bool dyn_ok(int c) { return c == 0 || c == 2 || c == 6 || c == 14; }
+// ... and for the grouped weight-gradient launch (gemm_dw2_kernel): the pipelined kernel with the staged epilogue.
+// Cfg 28 has never been built for it and stays out, to leave the built kernel set as it is.
+static constexpr bool dw2_ok(int c) { return kCfgs[c].family() == PipeCfg::PIPE && !kCfgs[c].direct && c != 28; }
+
+static constexpr int count_cfgs(bool (*ok)(int)) {
+    int n = 0;
+    for (int c = 0; c < kNumCfgs; ++c) n += ok(c) ? 1 : 0;
+    return n;
+}
+static_assert(count_cfgs(dw2_ok) == 32 && !dw2_ok(28), "grouped dW launch: cfgs 0-15, 25-27, 29-32, 38-46");
+static_assert(count_cfgs(dyn_ok) == 4 && kCfgs[0].plain() && kCfgs[2].plain() && kCfgs[6].plain() && kCfgs[14].plain(),
+              "device extents: the plain pipelined cfgs 0, 2, 6, 14");
+static_assert(has_colsum(2) && !has_colsum(16) && !has_colsum(33) && !has_colsum(38),
+              "in-kernel bias column sums: not warp-specialised, KS2 or 32x32 MFMA");
+
+// Calls f(std::integral_constant<int, C>{}) for the runtime index c in [0, N): one indexed call through a table of f's
+// N instantiations.  `if constexpr` on C inside f keeps a subset's kernels the only ones built.
+template <typename F, int C>
+static decltype(auto) call_cfg(F& f) {
+    return f(std::integral_constant<int, C>{});
+}
+template <typename F, size_t... I>
+static decltype(auto) with_cfg_impl(int c, F& f, std::index_sequence<I...>) {
+    static constexpr decltype(&call_cfg<F, 0>) table[] = {&call_cfg<F, (int)I>...};
+    return table[c](f);
+}
+template <int N, typename F>
+static decltype(auto) with_cfg(int c, F&& f) {
+    return with_cfg_impl(c, f, std::make_index_sequence<N>{});
+}
+
+// Launches kernel K with LDS bytes of dynamic shared memory through ERGM_LAUNCH (so a fork point armed on the stream
+// binds to it), raising K's dynamic-LDS limit before its first launch.  The attribute call's result is dropped on
+// purpose: a kernel left at the default limit fails its launch, which check_launch reports.
+template <auto K, size_t LDS, typename... Args>
+static void launch_lds(dim3 grid, dim3 block, hipStream_t s, const Args&... args) {
+    static const hipError_t once = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
+    (void)once;
+    ERGM_LAUNCH(K, grid, block, LDS, s, args...);
+}
+
 static thread_local int g_force_cfg = -1;    // ergm_gemm_tune: -1 = automatic
 static thread_local int g_force_split = 0;
 
@@ -1162,6 +1222,12 @@ struct GemmPlan {
 };
 
 static long tiles_of(int M, int N, int bm, int bn) { return (long)cdiv(M, bm) * cdiv(N, bn); }
+
+// Split-K workspace of a planned GEMM: the f32 slabs [split][M][N], then the bias gradient's partials [split][N].
+static size_t split_ws_bytes(const ergm_gemm_desc* d, const GemmPlan& p) {
+    if (p.split <= 1) return 0;
+    return (size_t)p.split * d->M * d->N * sizeof(float) + (d->bias_grad ? (size_t)p.split * d->N * sizeof(float) : 0);
+}
 
 // Layout / epilogue / output-type combinations instantiated for the pipelined kernels (the ones the
 // training step issues); everything else runs on the register-staged kernel.
@@ -1183,10 +1249,38 @@ static bool pipe_ok(const ergm_gemm_desc* d) {
 // (M, N, K, layouts); a small fixed table, written from the host only (plan creation / tuning).
 struct GemmOverride {
     int M, N, K, al, bl, cfg, split;
+    constexpr bool same_key(const GemmOverride& o) const {
+        return M == o.M && N == o.N && K == o.K && al == o.al && bl == o.bl;
+    }
 };
-static constexpr int kMaxOverrides = 64;
-static GemmOverride g_over[kMaxOverrides];
-static int g_n_over = 0;
+
+template <typename E>
+static const E* find_key(const E* t, int n, const E& key) {
+    for (int i = 0; i < n; ++i)
+        if (t[i].same_key(key)) return &t[i];
+    return nullptr;
+}
+
+// The runtime entries of one kind of override (E has same_key); callers hold g_over_mu.
+template <typename E, int CAP>
+struct OverrideTable {
+    E e[CAP];
+    int n = 0;
+    const E* find(const E& key) const { return find_key(e, n, key); }
+    bool set(const E& v) {  // false: the table is full
+        if (const E* o = find(v)) {
+            e[o - e] = v;
+            return true;
+        }
+        if (n == CAP) return false;
+        e[n++] = v;
+        return true;
+    }
+    void erase(const E& key) {
+        if (const E* o = find(key)) e[o - e] = e[--n];
+    }
+};
+static OverrideTable<GemmOverride, 64> g_over;
 static std::mutex g_over_mu;
 
 // Built-in entries measured by tools/step_tune.py inside the bench step (interleaved A/B against the
@@ -1222,23 +1316,14 @@ static constexpr GemmOverride kStepTuned[] = {
 };
 
 static bool find_override(const ergm_gemm_desc* d, int& cfg, int& split) {
+    const GemmOverride key{d->M, d->N, d->K, d->a_layout, d->b_layout, 0, 0};
     std::lock_guard<std::mutex> lk(g_over_mu);
-    for (int i = 0; i < g_n_over; ++i) {
-        const GemmOverride& o = g_over[i];
-        if (o.M == d->M && o.N == d->N && o.K == d->K && o.al == d->a_layout && o.bl == d->b_layout) {
-            cfg = o.cfg;
-            split = o.split;
-            return true;
-        }
-    }
-    for (const GemmOverride& o : kStepTuned) {
-        if (o.M == d->M && o.N == d->N && o.K == d->K && o.al == d->a_layout && o.bl == d->b_layout) {
-            cfg = o.cfg;
-            split = o.split;
-            return true;
-        }
-    }
-    return false;
+    const GemmOverride* o = g_over.find(key);
+    if (!o) o = find_key(kStepTuned, (int)std::size(kStepTuned), key);
+    if (!o) return false;
+    cfg = o->cfg;
+    split = o->split;
+    return true;
 }
 
 // Shape trace (ergm_gemm_trace): the distinct (M, N, K, layouts) of the ergm_gemm calls since enabled.
@@ -1320,101 +1405,41 @@ static GemmPlan plan_gemm(const ergm_gemm_desc* d) {
     return p;
 }
 
+// The kernel of configuration C.  DIRECT is passed apart from the table: split-K partials keep the staged epilogue.
+template <int C, bool AKM, bool BKN, int EPI, bool OB, bool DIRECT>
+static constexpr auto pipe_kernel() {
+    constexpr PipeCfg c = kCfgs[C];
+    if constexpr (c.family() == PipeCfg::KS2)
+        return gemm_ks2_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, AKM, BKN, EPI, OB>;
+    else if constexpr (c.family() == PipeCfg::WS)
+        return gemm_ws_kernel<c.bm, c.bn, c.wgm, c.wgn, c.np, c.ns, AKM, BKN, EPI, OB>;
+    else
+        return gemm_pipe_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, AKM, BKN, EPI, OB, DIRECT, c.il, c.mf>;
+}
+
 template <int C, bool AKM, bool BKN, int EPI, bool OB>
 static void launch_pipe_cfg(const GemmArgs& a, int split, hipStream_t s) {
     constexpr PipeCfg c = kCfgs[C];
-    constexpr int nthreads = 64 * (c.wgm * c.wgn * c.ks + c.np);
-    constexpr size_t lds = std::max((size_t)c.ns * c.ks * (c.bm + c.bn) * GEMM_BK * 2,
-                                    (size_t)(c.bm / c.wgm) * (c.bn + 4) * 4);
-    using KSplit = decltype(&gemm_pipe_kernel<16, 16, 1, 1, 2, AKM, BKN, ERGM_EPI_NONE, false>);
-    KSplit k_split, k_full;
-    if constexpr (c.ks == 2) {
-        k_split = gemm_ks2_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, AKM, BKN, ERGM_EPI_NONE, false>;
-        k_full = gemm_ks2_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, AKM, BKN, EPI, OB>;
-    } else if constexpr (c.np > 0) {
-        k_split = gemm_ws_kernel<c.bm, c.bn, c.wgm, c.wgn, c.np, c.ns, AKM, BKN, ERGM_EPI_NONE, false>;
-        k_full = gemm_ws_kernel<c.bm, c.bn, c.wgm, c.wgn, c.np, c.ns, AKM, BKN, EPI, OB>;
-    } else {
-        k_split = gemm_pipe_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, AKM, BKN, ERGM_EPI_NONE, false, false, c.il, c.mf>;
-        k_full = gemm_pipe_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, AKM, BKN, EPI, OB, c.direct, c.il, c.mf>;
-    }
-    static bool attr = (hipFuncSetAttribute((const void*)k_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        hipFuncSetAttribute((const void*)k_full, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        true);
-    (void)attr;
     dim3 grid(a.tiles_m * a.tiles_n, 1, split);
     if (a.xcd_split) grid = dim3(8 * a.tiles_m * a.tiles_n, 1, 1);  // split == 8, slice = XCD
-    ERGM_LAUNCH(split > 1 ? k_split : k_full, grid, dim3(nthreads), lds, s, a);
+    if (split > 1)  // f32 partials to the slabs; splitk_reduce_kernel runs the epilogue
+        launch_lds<pipe_kernel<C, AKM, BKN, ERGM_EPI_NONE, false, false>(), c.lds_bytes()>(grid, dim3(c.threads()), s, a);
+    else
+        launch_lds<pipe_kernel<C, AKM, BKN, EPI, OB, c.direct>(), c.lds_bytes()>(grid, dim3(c.threads()), s, a);
 }
 
 template <bool AKM, bool BKN, int EPI, bool OB>
 static void launch_pipe(const GemmArgs& a, int cfg, int split, hipStream_t s) {
-    switch (cfg) {
-        case 0: launch_pipe_cfg<0, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 1: launch_pipe_cfg<1, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 2: launch_pipe_cfg<2, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 3: launch_pipe_cfg<3, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 4: launch_pipe_cfg<4, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 5: launch_pipe_cfg<5, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 6: launch_pipe_cfg<6, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 7: launch_pipe_cfg<7, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 8: launch_pipe_cfg<8, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 9: launch_pipe_cfg<9, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 10: launch_pipe_cfg<10, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 11: launch_pipe_cfg<11, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 12: launch_pipe_cfg<12, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 13: launch_pipe_cfg<13, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 14: launch_pipe_cfg<14, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 15: launch_pipe_cfg<15, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 16: launch_pipe_cfg<16, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 17: launch_pipe_cfg<17, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 18: launch_pipe_cfg<18, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 19: launch_pipe_cfg<19, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 20: launch_pipe_cfg<20, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 21: launch_pipe_cfg<21, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 22: launch_pipe_cfg<22, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 23: launch_pipe_cfg<23, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 24: launch_pipe_cfg<24, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 25: launch_pipe_cfg<25, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 26: launch_pipe_cfg<26, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 27: launch_pipe_cfg<27, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 28: launch_pipe_cfg<28, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 29: launch_pipe_cfg<29, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 30: launch_pipe_cfg<30, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 31: launch_pipe_cfg<31, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 32: launch_pipe_cfg<32, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 33: launch_pipe_cfg<33, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 34: launch_pipe_cfg<34, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 35: launch_pipe_cfg<35, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 36: launch_pipe_cfg<36, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 37: launch_pipe_cfg<37, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 38: launch_pipe_cfg<38, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 39: launch_pipe_cfg<39, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 40: launch_pipe_cfg<40, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 41: launch_pipe_cfg<41, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 42: launch_pipe_cfg<42, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 43: launch_pipe_cfg<43, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 44: launch_pipe_cfg<44, AKM, BKN, EPI, OB>(a, split, s); break;
-        case 45: launch_pipe_cfg<45, AKM, BKN, EPI, OB>(a, split, s); break;
-        default: launch_pipe_cfg<46, AKM, BKN, EPI, OB>(a, split, s); break;
-    }
+    with_cfg<kNumCfgs>(cfg, [&](auto c) { launch_pipe_cfg<decltype(c)::value, AKM, BKN, EPI, OB>(a, split, s); });
 }
 
 // register-staged fallback (K % 64 != 0, odd N / leading dims, rarely used layout/epilogue pairs)
-template <int BM, int BN, bool AKM, bool BKN, int EPI, bool OB>
+template <int BM, int BN, bool AKM, bool BKN, int EPI, bool OB, bool DYN = false>
 static void launch_reg(const GemmArgs& a, int split, hipStream_t s) {
     constexpr size_t lds = std::max((size_t)2 * (BM + BN) * GEMM_BK * 2, (size_t)BM * (BN + 4) * 4);
-    static bool attr = (hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, AKM, BKN, EPI, OB>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, AKM, BKN, ERGM_EPI_NONE, false>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        true);
-    (void)attr;
-    dim3 grid(a.tiles_m * a.tiles_n, 1, split);
-    if (split > 1)
-        ERGM_LAUNCH((gemm_kernel<BM, BN, AKM, BKN, ERGM_EPI_NONE, false>), grid, dim3(GEMM_THREADS), lds, s, a);
-    else
-        ERGM_LAUNCH((gemm_kernel<BM, BN, AKM, BKN, EPI, OB>), grid, dim3(GEMM_THREADS), lds, s, a);
+    const dim3 grid(a.tiles_m * a.tiles_n, 1, split);
+    if (split > 1) launch_lds<gemm_kernel<BM, BN, AKM, BKN, ERGM_EPI_NONE, false, DYN>, lds>(grid, dim3(GEMM_THREADS), s, a);
+    else launch_lds<gemm_kernel<BM, BN, AKM, BKN, EPI, OB, DYN>, lds>(grid, dim3(GEMM_THREADS), s, a);
 }
 
 template <bool AKM, bool BKN, int EPI, bool OB>
@@ -1423,15 +1448,9 @@ static void launch_reg_any(const GemmArgs& a, const GemmPlan& p, hipStream_t s) 
     else launch_reg<64, 64, AKM, BKN, EPI, OB>(a, p.split, s);
 }
 
-// Layout/epilogue pairs the training step issues get the pipelined kernel family.
-template <bool AKM, bool BKN, int EPI, bool OB>
-static constexpr bool pipe_combo() {
-    return combo_ok(AKM, BKN, EPI, OB);
-}
-
 template <bool AKM, bool BKN, int EPI, bool OB>
 static void launch_any(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
-    if constexpr (pipe_combo<AKM, BKN, EPI, OB>()) {
+    if constexpr (combo_ok(AKM, BKN, EPI, OB)) {
         if (p.cfg >= 0) {
             launch_pipe<AKM, BKN, EPI, OB>(a, p.cfg, p.split, s);
             return;
@@ -1448,17 +1467,15 @@ static void launch_layout(const GemmArgs& a, const GemmPlan& p, int al, int bl, 
     else launch_any<true, true, EPI, OB>(a, p, s);
 }
 
-template <int EPI, bool OB>
+template <int EPI, bool OB, bool DYN = false>
 static void launch_reduce(const GemmArgs& a, int split, hipStream_t s) {
     size_t total = (size_t)a.M * a.N;
     int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
-    ERGM_LAUNCH((splitk_reduce_kernel<EPI, OB>), dim3(blocks), dim3(256), 0, s, a, split);
+    ERGM_LAUNCH((splitk_reduce_kernel<EPI, OB, DYN>), dim3(blocks), dim3(256), 0, s, a, split);
 }
 
 // ---- GEMMs with device-side extents (ergm_gemm_desc m_count_dev / k_count_dev / row_map) -----------------------
-// b_layout KN, epilogue NONE, f32 C.  The pipelined configurations instantiated for them:
-static constexpr bool dyn_cfg_ok(int cfg) { return cfg == 0 || cfg == 2 || cfg == 6 || cfg == 14; }
-
+// b_layout KN, epilogue NONE, f32 C; the pipelined configurations instantiated for them: dyn_ok.
 static bool is_dyn(const ergm_gemm_desc* d) { return d->m_count_dev || d->k_count_dev || d->row_map; }
 
 // Plan for the capacities: the row count is not known on the host, so the tile is the 128x128 one (2-stage ring,
@@ -1478,10 +1495,10 @@ static GemmPlan plan_dyn(const ergm_gemm_desc* d) {
         p.cfg = 2;
         if (!d->k_count_dev && d->split_k != 1) split = std::max(1, std::min(16, d->K / 512));
         int ocfg = -1, osplit = 1;
-        if (g_force_cfg >= 0 && dyn_cfg_ok(g_force_cfg)) {
+        if (g_force_cfg >= 0 && dyn_ok(g_force_cfg)) {
             p.cfg = g_force_cfg;
             if (g_force_split > 0) split = g_force_split;
-        } else if (d->split_k == 0 && find_override(d, ocfg, osplit) && dyn_cfg_ok(ocfg)) {
+        } else if (d->split_k == 0 && find_override(d, ocfg, osplit) && dyn_ok(ocfg)) {
             p.cfg = ocfg;
             split = osplit;
         }
@@ -1503,35 +1520,23 @@ static GemmPlan plan_dyn(const ergm_gemm_desc* d) {
 template <int C, bool AKM>
 static void launch_dyn_cfg(const GemmArgs& a, int split, hipStream_t s) {
     constexpr PipeCfg c = kCfgs[C];
-    static_assert(dyn_cfg_ok(C) && c.np == 0 && c.ks == 1 && !c.direct && c.il == 0 && c.mf == 16, "plain pipelined cfg");
-    constexpr size_t lds = std::max((size_t)c.ns * (c.bm + c.bn) * GEMM_BK * 2, (size_t)(c.bm / c.wgm) * (c.bn + 4) * 4);
-    auto k = gemm_pipe_dyn_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, AKM, true>;
-    static bool attr = (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
-    (void)attr;
     const dim3 grid = a.xcd_split ? dim3(8 * a.tiles_m * a.tiles_n, 1, split / 8) : dim3(a.tiles_m * a.tiles_n, 1, split);
-    ERGM_LAUNCH(k, grid, dim3(64 * c.wgm * c.wgn), lds, s, a);
+    launch_lds<gemm_pipe_dyn_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, AKM, true>, c.lds_bytes()>(
+        grid, dim3(c.threads()), s, a);
 }
 
 template <bool AKM>
 static void launch_dyn(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
-    switch (p.cfg) {
-        case 0: launch_dyn_cfg<0, AKM>(a, p.split, s); break;
-        case 2: launch_dyn_cfg<2, AKM>(a, p.split, s); break;
-        case 6: launch_dyn_cfg<6, AKM>(a, p.split, s); break;
-        case 14: launch_dyn_cfg<14, AKM>(a, p.split, s); break;
-        default: {  // register-staged 64x64 kernel: any K, N and leading dimensions
-            constexpr size_t lds = std::max((size_t)2 * (64 + 64) * GEMM_BK * 2, (size_t)64 * (64 + 4) * 4);
-            auto k = gemm_kernel<64, 64, AKM, true, ERGM_EPI_NONE, false, true>;
-            static bool attr = (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
-            (void)attr;
-            ERGM_LAUNCH(k, dim3(a.tiles_m * a.tiles_n, 1, p.split), dim3(GEMM_THREADS), lds, s, a);
-        }
-    }
-    if (p.split > 1) {
-        const size_t total = (size_t)a.M * a.N;
-        const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
-        ERGM_LAUNCH((splitk_reduce_kernel<ERGM_EPI_NONE, false, true>), dim3(blocks), dim3(256), 0, s, a, p.split);
-    }
+    // cfg -1, and any configuration not built for device extents: the register-staged 64x64 kernel (any K, N and
+    // leading dimensions)
+    const auto reg = [&] { launch_reg<64, 64, AKM, true, ERGM_EPI_NONE, false, true>(a, p.split, s); };
+    if (p.cfg < 0) reg();
+    else
+        with_cfg<kNumCfgs>(p.cfg, [&](auto c) {
+            if constexpr (dyn_ok(decltype(c)::value)) launch_dyn_cfg<decltype(c)::value, AKM>(a, p.split, s);
+            else reg();
+        });
+    if (p.split > 1) launch_reduce<ERGM_EPI_NONE, false, true>(a, p.split, s);
 }
 
 }  // namespace ergm
@@ -1539,9 +1544,14 @@ static void launch_dyn(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
 using namespace ergm;
 
 namespace ergm {
-// fp8 configurations (tile, wave grid, stages); a stage is (BM + BN) x 128 bytes
+// fp8 / MX configurations (tile, wave grid, stages)
 struct F8Cfg {
     int bm, bn, wgm, wgn, ns;
+    constexpr int threads() const { return 64 * wgm * wgn; }
+    // a stage holds row_bytes per operand row: 128 of e4m3, and for MX 4 more of e8m0 scales
+    constexpr size_t lds_bytes(int row_bytes) const {
+        return std::max((size_t)ns * (bm + bn) * row_bytes, (size_t)(bm / wgm) * (bn + 4) * 4);
+    }
 };
 static constexpr F8Cfg kF8Cfgs[] = {
     {128, 128, 2, 2, 3},  // 0
@@ -1553,35 +1563,31 @@ static constexpr F8Cfg kF8Cfgs[] = {
 static constexpr int kNumF8Cfgs = sizeof(kF8Cfgs) / sizeof(kF8Cfgs[0]);
 static thread_local int g_force_f8_cfg = -1;
 
-template <int C, int EPI, bool OB>
-static void launch_f8_cfg(const GemmArgs& a, hipStream_t s) {
-    constexpr F8Cfg c = kF8Cfgs[C];
-    constexpr size_t lds = std::max((size_t)c.ns * (c.bm + c.bn) * 128, (size_t)(c.bm / c.wgm) * (c.bn + 4) * 4);
-    auto k = gemm_f8_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, EPI, OB>;
-    static bool attr = (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
-    (void)attr;
-    ERGM_LAUNCH(k, dim3(a.tiles_m * a.tiles_n), dim3(64 * c.wgm * c.wgn), lds, s, a);
-}
-
 template <int EPI, bool OB>
 static void launch_f8(const GemmArgs& a, int cfg, hipStream_t s) {
-    switch (cfg) {
-        case 0: launch_f8_cfg<0, EPI, OB>(a, s); break;
-        case 1: launch_f8_cfg<1, EPI, OB>(a, s); break;
-        case 2: launch_f8_cfg<2, EPI, OB>(a, s); break;
-        case 3: launch_f8_cfg<3, EPI, OB>(a, s); break;
-        default: launch_f8_cfg<4, EPI, OB>(a, s); break;
-    }
+    with_cfg<kNumF8Cfgs>(cfg, [&](auto ci) {
+        constexpr F8Cfg c = kF8Cfgs[decltype(ci)::value];
+        launch_lds<gemm_f8_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, EPI, OB>, c.lds_bytes(128)>(
+            dim3(a.tiles_m * a.tiles_n), dim3(c.threads()), s, a);
+    });
+}
+
+template <int EPI, bool OB, bool QMX>
+static void launch_mx(const GemmArgs& a, int cfg, hipStream_t s) {
+    with_cfg<kNumF8Cfgs>(cfg, [&](auto ci) {
+        constexpr F8Cfg c = kF8Cfgs[decltype(ci)::value];
+        launch_lds<gemm_mx_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, EPI, OB, QMX>, c.lds_bytes(132)>(
+            dim3(a.tiles_m * a.tiles_n), dim3(c.threads()), s, a);
+    });
 }
 
 // Per-shape overrides of the fp8 / MX tile configuration (ergm_gemm_f8_set_override: the in-step tuner) and the
 // built-in entries it measured; keyed on (M, N, K).
 struct F8Override {
     int M, N, K, cfg;
+    constexpr bool same_key(const F8Override& o) const { return M == o.M && N == o.N && K == o.K; }
 };
-static constexpr int kMaxF8Overrides = 32;
-static F8Override g_f8_over[kMaxF8Overrides];
-static int g_n_f8_over = 0;
+static OverrideTable<F8Override, 32> g_f8_over;
 static constexpr F8Override kF8StepTuned[] = {
     // config 5 (GPT-2-medium, B=32, S=128; forward chains of M = 2048): the MX c_fc GEMM on the 256 x 256 tile
     // (tools/step_tune.py --config c5 --f8: 21.06 -> 20.85 ms/step, profiles/r05_step_tune_c5_f8.txt)
@@ -1591,12 +1597,12 @@ static constexpr F8Override kF8StepTuned[] = {
 static int plan_f8(int M, int N, int K) {
     if (g_force_f8_cfg >= 0) return g_force_f8_cfg;
     {
+        const F8Override key{M, N, K, 0};
         std::lock_guard<std::mutex> lk(g_over_mu);
-        for (int i = 0; i < g_n_f8_over; ++i)
-            if (g_f8_over[i].M == M && g_f8_over[i].N == N && g_f8_over[i].K == K) return g_f8_over[i].cfg;
+        const F8Override* o = g_f8_over.find(key);
+        if (!o) o = find_key(kF8StepTuned, (int)std::size(kF8StepTuned), key);
+        if (o) return o->cfg;
     }
-    for (const F8Override& o : kF8StepTuned)
-        if (o.cfg >= 0 && o.M == M && o.N == N && o.K == K) return o.cfg;
     const long t128 = tiles_of(M, N, 128, 128);
     if (t128 >= 4000) return 3;
     if (t128 >= 512) return 1;
@@ -1604,64 +1610,8 @@ static int plan_f8(int M, int N, int K) {
     return 4;
 }
 
-}  // namespace ergm
-
-namespace ergm {
-template <int C, int EPI, bool OB, bool QMX>
-static void launch_mx_cfg(const GemmArgs& a, hipStream_t s) {
-    constexpr F8Cfg c = kF8Cfgs[C];
-    constexpr size_t stage = (size_t)(c.bm + c.bn) * 132;  // operand bytes (128 per row) + scale bytes (4 per row)
-    constexpr size_t lds = std::max((size_t)c.ns * stage, (size_t)(c.bm / c.wgm) * (c.bn + 4) * 4);
-    auto k = gemm_mx_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, EPI, OB, QMX>;
-    static bool attr = (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
-    (void)attr;
-    ERGM_LAUNCH(k, dim3(a.tiles_m * a.tiles_n), dim3(64 * c.wgm * c.wgn), lds, s, a);
-}
-template <int EPI, bool OB, bool QMX>
-static void launch_mx(const GemmArgs& a, int cfg, hipStream_t s) {
-    switch (cfg) {
-        case 0: launch_mx_cfg<0, EPI, OB, QMX>(a, s); break;
-        case 1: launch_mx_cfg<1, EPI, OB, QMX>(a, s); break;
-        case 2: launch_mx_cfg<2, EPI, OB, QMX>(a, s); break;
-        case 3: launch_mx_cfg<3, EPI, OB, QMX>(a, s); break;
-        default: launch_mx_cfg<4, EPI, OB, QMX>(a, s); break;
-    }
-}
-}  // namespace ergm
-
-extern "C" int ergm_gemm_mx(const ergm_gemm_desc* d, const void* A, const void* a_scale, int ld_sa, const void* B,
-                            const void* b_scale, int ld_sb, void* C, void* q_out, void* q_scale, int ld_q, int ld_qs,
-                            void* stream) {
-    using namespace ergm;
-    ERGM_CHECK_ARG(d && A && B && C && a_scale && b_scale, "ergm_gemm_mx: null argument");
-    ERGM_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0 && d->K % 128 == 0, "ergm_gemm_mx: K=%d must be a multiple of 128",
-                   d->K);
-    ERGM_CHECK_ARG(d->a_layout == ERGM_MK && d->b_layout == ERGM_NK, "ergm_gemm_mx: A [M][K] and B [N][K] only");
-    ERGM_CHECK_ARG(d->lda >= d->K && d->ldb >= d->K && d->lda % 16 == 0 && d->ldb % 16 == 0,
-                   "ergm_gemm_mx: lda/ldb >= K, multiples of 16 bytes");
-    ERGM_CHECK_ARG(ld_sa >= d->M && ld_sb >= d->N, "ergm_gemm_mx: scale pitches ld_sa >= M, ld_sb >= N (rows)");
-    ERGM_CHECK_ARG(aligned16(A) && aligned16(B) && (reinterpret_cast<uintptr_t>(a_scale) & 3) == 0 &&
-                       (reinterpret_cast<uintptr_t>(b_scale) & 3) == 0,
-                   "ergm_gemm_mx: operand / scale alignment");
-    ERGM_CHECK_ARG(d->N % 8 == 0 && d->ldc % 8 == 0 && d->ldc >= d->N, "ergm_gemm_mx: N, ldc multiples of 8");
-    ERGM_CHECK_ARG(d->c_dtype == ERGM_F32 || d->c_dtype == ERGM_BF16, "ergm_gemm_mx: bad c_dtype");
-    const int e = d->epilogue;
-    const bool bf_epi = e == ERGM_EPI_BIAS || e == ERGM_EPI_BIAS_GELU || e == ERGM_EPI_GELU_BWD;
-    ERGM_CHECK_ARG(e == ERGM_EPI_NONE || (bf_epi && d->c_dtype == ERGM_BF16) ||
-                       (e == ERGM_EPI_BIAS_RESID && d->c_dtype == ERGM_F32),
-                   "ergm_gemm_mx: epilogue %d with c_dtype %d not supported", e, d->c_dtype);
-    ERGM_CHECK_ARG(!(e == ERGM_EPI_BIAS_RESID || e == ERGM_EPI_GELU_BWD) || (d->aux && d->ld_aux % 8 == 0),
-                   "ergm_gemm_mx: epilogue %d needs aux", e);
-    ERGM_CHECK_ARG(e != ERGM_EPI_BIAS_GELU || (d->aux_out && d->ld_aux_out % 8 == 0), "ergm_gemm_mx: GELU needs aux_out");
-    ERGM_CHECK_ARG(!q_out || (q_scale && (e == ERGM_EPI_BIAS_GELU || e == ERGM_EPI_GELU_BWD) && d->N % 32 == 0 &&
-                              ld_q >= d->N && ld_q % 8 == 0 && ld_qs >= d->M),
-                   "ergm_gemm_mx: the MX copy of C needs a GELU / GELU' epilogue, N % 32 == 0 and its buffers");
-    {  // the shape trace lists the fp8 / MX GEMMs with a_layout 16 (ergm_gemm_f8_set_override's keys)
-        ergm_gemm_desc t = *d;
-        t.a_layout = 16;
-        trace_shape(&t);
-    }
-    const int cfg = plan_f8(d->M, d->N, d->K);
+// The kernel arguments every GEMM entry point fills alike, for bm x bn tiles; the rest stays zero.
+static GemmArgs fill_args(const ergm_gemm_desc* d, const void* A, const void* B, void* C, int bm, int bn) {
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = reinterpret_cast<const __bf16*>(A);
@@ -1672,19 +1622,70 @@ extern "C" int ergm_gemm_mx(const ergm_gemm_desc* d, const void* A, const void* 
     a.alpha = d->alpha; a.alpha_dev = d->alpha_dev;
     a.bias = d->bias; a.aux = d->aux; a.ld_aux = d->ld_aux;
     a.aux_out = d->aux_out; a.ld_aux_out = d->ld_aux_out;
-    a.tiles_m = cdiv(d->M, kF8Cfgs[cfg].bm);
-    a.tiles_n = cdiv(d->N, kF8Cfgs[cfg].bn);
+    a.tiles_m = cdiv(d->M, bm); a.tiles_n = cdiv(d->N, bn);
+    // stream the larger operand once: walk along the dimension of the smaller operand
     a.sweep_m = (long)d->M < (long)d->N ? 1 : 0;
+    a.drop = drop_site_of(d->dropout, d->N);
+    return a;
+}
+
+// The checks ergm_gemm_f8 and ergm_gemm_mx share; fn is the entry point's name in the messages.  What differs stays
+// with each: the scales and the operand / scale alignment message, the allowed epilogues and their aux, q_out.
+static int check_lowp_desc(const char* fn, const ergm_gemm_desc* d, const void* A, const void* B, const void* C,
+                           const void* a_scale, const void* b_scale) {
+    ERGM_CHECK_ARG(d && A && B && C && a_scale && b_scale, "%s: null argument", fn);
+    ERGM_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0 && d->K % 128 == 0, "%s: K=%d must be a multiple of 128", fn, d->K);
+    ERGM_CHECK_ARG(d->a_layout == ERGM_MK && d->b_layout == ERGM_NK, "%s: A [M][K] and B [N][K] only", fn);
+    ERGM_CHECK_ARG(d->lda >= d->K && d->ldb >= d->K && d->lda % 16 == 0 && d->ldb % 16 == 0,
+                   "%s: lda/ldb >= K, multiples of 16 bytes", fn);
+    ERGM_CHECK_ARG(d->N % 8 == 0 && d->ldc % 8 == 0 && d->ldc >= d->N, "%s: N, ldc multiples of 8", fn);
+    ERGM_CHECK_ARG(d->c_dtype == ERGM_F32 || d->c_dtype == ERGM_BF16, "%s: bad c_dtype", fn);
+    ERGM_CHECK_ARG(d->epilogue != ERGM_EPI_BIAS_GELU || (d->aux_out && d->ld_aux_out % 8 == 0),
+                   "%s: GELU needs aux_out", fn);
+    ERGM_TRY(check_dropout(d->dropout));
+    ERGM_CHECK_ARG(!d->dropout || d->dropout->p == 0.f || d->epilogue == ERGM_EPI_BIAS_RESID,
+                   "%s: dropout applies to the BIAS_RESID epilogue only", fn);
+    return ERGM_OK;
+}
+
+// Plans a checked fp8 / MX GEMM and fills the arguments the two share; returns the index into kF8Cfgs.
+static int plan_lowp(const ergm_gemm_desc* d, const void* A, const void* B, void* C, GemmArgs& a) {
+    ergm_gemm_desc t = *d;  // the shape trace lists the fp8 / MX GEMMs with a_layout 16 (ergm_gemm_f8_set_override's keys)
+    t.a_layout = 16;
+    trace_shape(&t);
+    const int cfg = plan_f8(d->M, d->N, d->K);
+    a = fill_args(d, A, B, C, kF8Cfgs[cfg].bm, kF8Cfgs[cfg].bn);
+    return cfg;
+}
+}  // namespace ergm
+
+extern "C" int ergm_gemm_mx(const ergm_gemm_desc* d, const void* A, const void* a_scale, int ld_sa, const void* B,
+                            const void* b_scale, int ld_sb, void* C, void* q_out, void* q_scale, int ld_q, int ld_qs,
+                            void* stream) {
+    using namespace ergm;
+    ERGM_TRY(check_lowp_desc("ergm_gemm_mx", d, A, B, C, a_scale, b_scale));
+    ERGM_CHECK_ARG(ld_sa >= d->M && ld_sb >= d->N, "ergm_gemm_mx: scale pitches ld_sa >= M, ld_sb >= N (rows)");
+    ERGM_CHECK_ARG(aligned16(A) && aligned16(B) && (reinterpret_cast<uintptr_t>(a_scale) & 3) == 0 &&
+                       (reinterpret_cast<uintptr_t>(b_scale) & 3) == 0,
+                   "ergm_gemm_mx: operand / scale alignment");
+    const int e = d->epilogue;
+    const bool bf_epi = e == ERGM_EPI_BIAS || e == ERGM_EPI_BIAS_GELU || e == ERGM_EPI_GELU_BWD;
+    ERGM_CHECK_ARG(e == ERGM_EPI_NONE || (bf_epi && d->c_dtype == ERGM_BF16) ||
+                       (e == ERGM_EPI_BIAS_RESID && d->c_dtype == ERGM_F32),
+                   "ergm_gemm_mx: epilogue %d with c_dtype %d not supported", e, d->c_dtype);
+    ERGM_CHECK_ARG(!(e == ERGM_EPI_BIAS_RESID || e == ERGM_EPI_GELU_BWD) || (d->aux && d->ld_aux % 8 == 0),
+                   "ergm_gemm_mx: epilogue %d needs aux", e);
+    ERGM_CHECK_ARG(!q_out || (q_scale && (e == ERGM_EPI_BIAS_GELU || e == ERGM_EPI_GELU_BWD) && d->N % 32 == 0 &&
+                              ld_q >= d->N && ld_q % 8 == 0 && ld_qs >= d->M),
+                   "ergm_gemm_mx: the MX copy of C needs a GELU / GELU' epilogue, N % 32 == 0 and its buffers");
+    GemmArgs a;
+    const int cfg = plan_lowp(d, A, B, C, a);
     a.a_mx = reinterpret_cast<const uint8_t*>(a_scale);
     a.b_mx = reinterpret_cast<const uint8_t*>(b_scale);
     a.ld_sa = ld_sa; a.ld_sb = ld_sb;
     a.q_out = reinterpret_cast<uint8_t*>(q_out);
     a.q_sc = reinterpret_cast<uint8_t*>(q_scale);
     a.ld_q = ld_q; a.ld_qs = ld_qs;
-    ERGM_TRY(check_dropout(d->dropout));
-    ERGM_CHECK_ARG(!d->dropout || d->dropout->p == 0.f || e == ERGM_EPI_BIAS_RESID,
-                   "ergm_gemm_mx: dropout applies to the BIAS_RESID epilogue only");
-    a.drop = drop_site_of(d->dropout, d->N);
     hipStream_t s = as_stream(stream);
     const bool ob = d->c_dtype == ERGM_BF16;
     switch (e) {
@@ -1710,15 +1711,8 @@ extern "C" int ergm_gemm_f8_set_override(int M, int N, int K, int cfg) {
     using namespace ergm;
     ERGM_CHECK_ARG(cfg >= -1 && cfg < kNumF8Cfgs, "gemm_f8_set_override: cfg in [-1, %d)", kNumF8Cfgs);
     std::lock_guard<std::mutex> lk(g_over_mu);
-    for (int i = 0; i < g_n_f8_over; ++i)
-        if (g_f8_over[i].M == M && g_f8_over[i].N == N && g_f8_over[i].K == K) {
-            if (cfg < 0) g_f8_over[i] = g_f8_over[--g_n_f8_over];
-            else g_f8_over[i].cfg = cfg;
-            return ERGM_OK;
-        }
-    if (cfg < 0) return ERGM_OK;
-    ERGM_CHECK_ARG(g_n_f8_over < kMaxF8Overrides, "gemm_f8_set_override: table full");
-    g_f8_over[g_n_f8_over++] = F8Override{M, N, K, cfg};
+    if (cfg < 0) g_f8_over.erase(F8Override{M, N, K, cfg});
+    else ERGM_CHECK_ARG(g_f8_over.set(F8Override{M, N, K, cfg}), "gemm_f8_set_override: table full");
     return ERGM_OK;
 }
 
@@ -1731,15 +1725,8 @@ extern "C" int ergm_gemm_f8_tune(int cfg) {
 extern "C" int ergm_gemm_f8(const ergm_gemm_desc* d, const void* A, const float* a_scale, const void* B,
                             const float* b_scale, void* C, void* stream) {
     using namespace ergm;
-    ERGM_CHECK_ARG(d && A && B && C && a_scale && b_scale, "ergm_gemm_f8: null argument");
-    ERGM_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0 && d->K % 128 == 0, "ergm_gemm_f8: K=%d must be a multiple of 128",
-                   d->K);
-    ERGM_CHECK_ARG(d->a_layout == ERGM_MK && d->b_layout == ERGM_NK, "ergm_gemm_f8: A [M][K] and B [N][K] only");
-    ERGM_CHECK_ARG(d->lda >= d->K && d->ldb >= d->K && d->lda % 16 == 0 && d->ldb % 16 == 0,
-                   "ergm_gemm_f8: lda/ldb >= K, multiples of 16 bytes");
+    ERGM_TRY(check_lowp_desc("ergm_gemm_f8", d, A, B, C, a_scale, b_scale));
     ERGM_CHECK_ARG(aligned16(A) && aligned16(B) && aligned16(b_scale), "ergm_gemm_f8: 16-byte alignment");
-    ERGM_CHECK_ARG(d->N % 8 == 0 && d->ldc % 8 == 0 && d->ldc >= d->N, "ergm_gemm_f8: N, ldc multiples of 8");
-    ERGM_CHECK_ARG(d->c_dtype == ERGM_F32 || d->c_dtype == ERGM_BF16, "ergm_gemm_f8: bad c_dtype");
     const int e = d->epilogue;
     ERGM_CHECK_ARG((e == ERGM_EPI_NONE || e == ERGM_EPI_BIAS || e == ERGM_EPI_BIAS_GELU) ? d->c_dtype == ERGM_BF16 ||
                        e == ERGM_EPI_NONE
@@ -1747,32 +1734,10 @@ extern "C" int ergm_gemm_f8(const ergm_gemm_desc* d, const void* A, const float*
                                                                                               d->c_dtype == ERGM_F32,
                    "ergm_gemm_f8: epilogue %d with c_dtype %d not supported", e, d->c_dtype);
     ERGM_CHECK_ARG(e != ERGM_EPI_BIAS_RESID || (d->aux && d->ld_aux % 8 == 0), "ergm_gemm_f8: residual needs aux");
-    ERGM_CHECK_ARG(e != ERGM_EPI_BIAS_GELU || (d->aux_out && d->ld_aux_out % 8 == 0), "ergm_gemm_f8: GELU needs aux_out");
-    {  // the shape trace lists the fp8 / MX GEMMs with a_layout 16 (ergm_gemm_f8_set_override's keys)
-        ergm_gemm_desc t = *d;
-        t.a_layout = 16;
-        trace_shape(&t);
-    }
-    const int cfg = plan_f8(d->M, d->N, d->K);
     GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A = reinterpret_cast<const __bf16*>(A);
-    a.B = reinterpret_cast<const __bf16*>(B);
-    a.C = C;
-    a.M = d->M; a.N = d->N; a.K = d->K;
-    a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
-    a.alpha = d->alpha; a.alpha_dev = d->alpha_dev;
-    a.bias = d->bias; a.aux = d->aux; a.ld_aux = d->ld_aux;
-    a.aux_out = d->aux_out; a.ld_aux_out = d->ld_aux_out;
-    a.tiles_m = cdiv(d->M, kF8Cfgs[cfg].bm);
-    a.tiles_n = cdiv(d->N, kF8Cfgs[cfg].bn);
-    a.sweep_m = (long)d->M < (long)d->N ? 1 : 0;
+    const int cfg = plan_lowp(d, A, B, C, a);
     a.a_scale = a_scale;
     a.b_scale = b_scale;
-    ERGM_TRY(check_dropout(d->dropout));
-    ERGM_CHECK_ARG(!d->dropout || d->dropout->p == 0.f || e == ERGM_EPI_BIAS_RESID,
-                   "ergm_gemm_f8: dropout applies to the BIAS_RESID epilogue only");
-    a.drop = drop_site_of(d->dropout, d->N);
     hipStream_t s = as_stream(stream);
     const bool ob = d->c_dtype == ERGM_BF16;
     switch (e) {
@@ -1796,30 +1761,16 @@ extern "C" int ergm_gemm_tune(int cfg, int split) {
 
 extern "C" size_t ergm_gemm_workspace_size(const ergm_gemm_desc* d) {
     if (!d) return 0;
-    GemmPlan p = is_dyn(d) ? plan_dyn(d) : plan_gemm(d);  // device-side extents: sized for the capacities M, K
-    if (p.split <= 1) return 0;
-    return (size_t)p.split * d->M * d->N * sizeof(float) + (d->bias_grad ? (size_t)p.split * d->N * sizeof(float) : 0);
+    return split_ws_bytes(d, is_dyn(d) ? plan_dyn(d) : plan_gemm(d));  // device-side extents: sized for the capacities M, K
 }
 
 extern "C" int ergm_gemm_set_override(int M, int N, int K, int a_layout, int b_layout, int cfg, int split) {
     ERGM_CHECK_ARG(cfg >= -1 && cfg < kNumCfgs && split >= 1 && split <= 16, "gemm_set_override: cfg in [-1, %d)",
                    kNumCfgs);
+    const GemmOverride o{M, N, K, a_layout, b_layout, cfg, split};
     std::lock_guard<std::mutex> lk(g_over_mu);
-    for (int i = 0; i < g_n_over; ++i) {
-        GemmOverride& o = g_over[i];
-        if (o.M == M && o.N == N && o.K == K && o.al == a_layout && o.bl == b_layout) {
-            if (cfg < 0) {
-                o = g_over[--g_n_over];
-            } else {
-                o.cfg = cfg;
-                o.split = split;
-            }
-            return ERGM_OK;
-        }
-    }
-    if (cfg < 0) return ERGM_OK;
-    ERGM_CHECK_ARG(g_n_over < kMaxOverrides, "gemm_set_override: table full");
-    g_over[g_n_over++] = GemmOverride{M, N, K, a_layout, b_layout, cfg, split};
+    if (cfg < 0) g_over.erase(o);
+    else ERGM_CHECK_ARG(g_over.set(o), "gemm_set_override: table full");
     return ERGM_OK;
 }
 
@@ -1837,37 +1788,17 @@ extern "C" int ergm_gemm_trace(int on, int* shapes, int max_shapes) {
 namespace ergm {
 // Kernel arguments of one planned GEMM (split-K slabs are set by the caller).
 static GemmArgs make_args(const ergm_gemm_desc* d, const void* A, const void* B, void* C, const GemmPlan& p) {
-    GemmArgs a;
-    a.A = reinterpret_cast<const __bf16*>(A);
-    a.B = reinterpret_cast<const __bf16*>(B);
-    a.C = C;
-    a.M = d->M; a.N = d->N; a.K = d->K;
-    a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
-    a.alpha = d->alpha; a.alpha_dev = d->alpha_dev;
-    a.bias = d->bias; a.aux = d->aux; a.ld_aux = d->ld_aux;
-    a.aux_out = d->aux_out; a.ld_aux_out = d->ld_aux_out;
-    a.tiles_m = cdiv(d->M, p.bm); a.tiles_n = cdiv(d->N, p.bn);
-    // stream the larger operand once: walk along the dimension of the smaller operand
-    a.sweep_m = (long)d->M < (long)d->N ? 1 : 0;
+    GemmArgs a = fill_args(d, A, B, C, p.bm, p.bn);
     a.k_per_split = p.kps;
-    a.slab = nullptr;
-    a.a_scale = a.b_scale = nullptr;
-    a.drop = drop_site_of(d->dropout, d->N);
     // the vocabulary-wide bf16 logits (206 MB at C2) are streamed out with non-temporal stores so they
     // do not evict the operands of the kernels running beside the LM head (C2 step +0.5-1 %,
     // profiles/r01_overlap_experiments.txt #14) ... and so are the f32 weight gradients (A = activationsᵀ),
     // consumed later by the optimizer / the all-reduce (C5 +0.4-0.8 %, C2 neutral: #17)
-    static const bool nt_wide = [] {  // ERGM_NT_WIDE=0: vocabulary-wide bf16 outputs (the logits) stored normally (A/B)
-        const char* e = getenv("ERGM_NT_WIDE");
-        return !e || atoi(e) != 0;
-    }();
-    a.nt_store = (nt_wide && d->c_dtype == ERGM_BF16 && d->N >= 32768) ||
+    a.nt_store = (d->c_dtype == ERGM_BF16 && d->N >= 32768) ||
                  (d->c_dtype == ERGM_F32 && d->a_layout == ERGM_KM && d->epilogue == ERGM_EPI_NONE);
-    // the in-GEMM bias gradient runs in the pipelined (non-warp-specialised) kernels; others use a column-sum pass
-    const bool cs_in = d->bias_grad && p.cfg >= 0 && kCfgs[p.cfg].np == 0 && kCfgs[p.cfg].ks == 1 && kCfgs[p.cfg].mf == 16;
-    a.colsum = cs_in ? d->bias_grad : nullptr;
-    a.colsum_part = nullptr;
-    a.xcd_split = p.xcd && p.cfg >= 0 && kCfgs[p.cfg].np == 0 && kCfgs[p.cfg].ks == 1 && kCfgs[p.cfg].mf == 16 ? 1 : 0;
+    // the in-GEMM bias gradient where the configuration has it; ergm_gemm runs a column-sum pass for the others
+    a.colsum = p.cfg >= 0 && has_colsum(p.cfg) ? d->bias_grad : nullptr;
+    a.xcd_split = p.xcd && p.cfg >= 0 && kCfgs[p.cfg].xcd_ok() ? 1 : 0;
     a.m_dev = d->m_count_dev;
     a.k_dev = d->k_count_dev;
     a.row_map = d->row_map;
@@ -1921,28 +1852,21 @@ extern "C" int ergm_gemm(const ergm_gemm_desc* d, const void* A, const void* B, 
     const int e = d->epilogue;
     trace_shape(d);
     hipStream_t s = as_stream(stream);
-    if (is_dyn(d)) {
-        const GemmPlan p = plan_dyn(d);
-        GemmArgs a = make_args(d, A, B, C, p);
-        if (p.split > 1) {
-            const size_t need = (size_t)p.split * d->M * d->N * sizeof(float);
-            ERGM_CHECK_ARG(ws && ws_bytes >= need, "ergm_gemm: split-K %d needs %zu workspace bytes (got %zu)", p.split,
-                           need, ws_bytes);
-            a.slab = reinterpret_cast<float*>(ws);
-        }
-        if (d->a_layout == ERGM_KM) launch_dyn<true>(a, p, s);
-        else launch_dyn<false>(a, p, s);
-        return check_launch("ergm_gemm");
-    }
-    GemmPlan p = plan_gemm(d);
+    const bool dyn = is_dyn(d);
+    const GemmPlan p = dyn ? plan_dyn(d) : plan_gemm(d);
     GemmArgs a = make_args(d, A, B, C, p);
     const bool cs_in = a.colsum != nullptr;
     if (p.split > 1) {
-        size_t need = (size_t)p.split * d->M * d->N * sizeof(float) + (d->bias_grad ? (size_t)p.split * d->N * 4 : 0);
+        const size_t need = split_ws_bytes(d, p);
         ERGM_CHECK_ARG(ws && ws_bytes >= need, "ergm_gemm: split-K %d needs %zu workspace bytes (got %zu)", p.split,
                        need, ws_bytes);
         a.slab = reinterpret_cast<float*>(ws);
         if (cs_in) a.colsum_part = a.slab + (size_t)p.split * d->M * d->N;
+    }
+    if (dyn) {  // b_layout KN, epilogue NONE, f32 C, no bias_grad (validate_desc)
+        if (d->a_layout == ERGM_KM) launch_dyn<true>(a, p, s);
+        else launch_dyn<false>(a, p, s);
+        return check_launch("ergm_gemm");
     }
     const bool ob = d->c_dtype == ERGM_BF16;
 #define ERGM_EPI_CASE(E)                                                  \
@@ -1970,20 +1894,10 @@ extern "C" int ergm_gemm(const ergm_gemm_desc* d, const void* A, const void* B, 
 }
 
 namespace ergm {
-template <int C, int EPI = ERGM_EPI_NONE>
-static void launch_dw2_cfg(const GemmArgs2& g, int nblocks, hipStream_t s) {
-    constexpr PipeCfg c = kCfgs[C];
-    static_assert(c.np == 0 && !c.direct, "grouped dW launch: pipelined kernels with the staged epilogue only");
-    constexpr size_t lds = std::max((size_t)c.ns * (c.bm + c.bn) * GEMM_BK * 2, (size_t)(c.bm / c.wgm) * (c.bn + 4) * 4);
-    auto k = gemm_dw2_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, c.il, EPI, c.mf>;
-    static bool attr = (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
-    (void)attr;
-    ERGM_LAUNCH(k, dim3(nblocks), dim3(64 * c.wgm * c.wgn), lds, s, g);
-}
-
 // Two weight-gradient GEMMs (a_layout KM, b_layout KN, epilogue NONE, f32 C) in one launch when both plan
 // to the same unsplit pipelined configuration; ERGM_EUNSUPPORTED (nothing launched) otherwise, and the caller
-// issues them one by one.  launch = false: only the check.  Same kernel body and tile order as ergm_gemm: the results are bit-identical.
+// issues them one by one.  launch = false: only the check, which is the whole decision: a pair it accepts is launched,
+// and nothing is traced for one it refuses.  Same kernel body and tile order as ergm_gemm: the results are bit-identical.
 int gemm_dw_pair(const ergm_gemm_desc* const d[2], const void* const A[2], const void* const B[2], void* const C[2],
                  void* stream, bool launch) {
     for (int i = 0; i < 2; ++i) {
@@ -1994,11 +1908,10 @@ int gemm_dw_pair(const ergm_gemm_desc* const d[2], const void* const A[2], const
     }
     GemmPlan p[2] = {plan_gemm(d[0]), plan_gemm(d[1])};
     const int cfg = p[0].cfg;
-    if (cfg < 0 || (cfg >= 16 && cfg < 38 && kCfgs[cfg].il == 0) || kCfgs[cfg].ks != 1 || p[1].cfg != cfg ||
-        p[0].split != 1 ||
-        p[1].split != 1 ||
-        p[0].xcd || p[1].xcd || kCfgs[cfg].np != 0 || kCfgs[cfg].direct)
+    if (cfg < 0 || !dw2_ok(cfg) || p[1].cfg != cfg || p[0].split != 1 || p[1].split != 1 || p[0].xcd || p[1].xcd)
         return ERGM_EUNSUPPORTED;
+    // the grouped kernel has no column-sum pass behind it: a bias gradient needs the in-kernel sums
+    if ((d[0]->bias_grad || d[1]->bias_grad) && !has_colsum(cfg)) return ERGM_EUNSUPPORTED;
     // only pairs whose problems each leave CUs idle: grouping two chip-filling GEMMs measured slower (C5:
     // 264 + 288 tiles, step +1.2 %); C2's pairs (150 + 168, 156 + 156 tiles) gain 0.4 %
     if (tiles_of(d[0]->M, d[0]->N, p[0].bm, p[0].bn) >= 256 || tiles_of(d[1]->M, d[1]->N, p[1].bm, p[1].bn) >= 256)
@@ -2012,41 +1925,15 @@ int gemm_dw_pair(const ergm_gemm_desc* const d[2], const void* const A[2], const
     g.b1 = (n0 + 7) & ~7;
     const int nb = g.b1 + n1;
     hipStream_t s = as_stream(stream);
-    switch (cfg) {
-        case 0: launch_dw2_cfg<0>(g, nb, s); break;
-        case 1: launch_dw2_cfg<1>(g, nb, s); break;
-        case 2: launch_dw2_cfg<2>(g, nb, s); break;
-        case 3: launch_dw2_cfg<3>(g, nb, s); break;
-        case 4: launch_dw2_cfg<4>(g, nb, s); break;
-        case 5: launch_dw2_cfg<5>(g, nb, s); break;
-        case 6: launch_dw2_cfg<6>(g, nb, s); break;
-        case 7: launch_dw2_cfg<7>(g, nb, s); break;
-        case 8: launch_dw2_cfg<8>(g, nb, s); break;
-        case 9: launch_dw2_cfg<9>(g, nb, s); break;
-        case 10: launch_dw2_cfg<10>(g, nb, s); break;
-        case 11: launch_dw2_cfg<11>(g, nb, s); break;
-        case 12: launch_dw2_cfg<12>(g, nb, s); break;
-        case 13: launch_dw2_cfg<13>(g, nb, s); break;
-        case 14: launch_dw2_cfg<14>(g, nb, s); break;
-        case 15: launch_dw2_cfg<15>(g, nb, s); break;
-        case 25: launch_dw2_cfg<25>(g, nb, s); break;
-        case 26: launch_dw2_cfg<26>(g, nb, s); break;
-        case 27: launch_dw2_cfg<27>(g, nb, s); break;
-        case 29: launch_dw2_cfg<29>(g, nb, s); break;
-        case 30: launch_dw2_cfg<30>(g, nb, s); break;
-        case 31: launch_dw2_cfg<31>(g, nb, s); break;
-        case 32: launch_dw2_cfg<32>(g, nb, s); break;
-        case 38: launch_dw2_cfg<38>(g, nb, s); break;
-        case 39: launch_dw2_cfg<39>(g, nb, s); break;
-        case 40: launch_dw2_cfg<40>(g, nb, s); break;
-        case 41: launch_dw2_cfg<41>(g, nb, s); break;
-        case 42: launch_dw2_cfg<42>(g, nb, s); break;
-        case 43: launch_dw2_cfg<43>(g, nb, s); break;
-        case 44: launch_dw2_cfg<44>(g, nb, s); break;
-        case 45: launch_dw2_cfg<45>(g, nb, s); break;
-        case 46: launch_dw2_cfg<46>(g, nb, s); break;
-        default: return ERGM_EUNSUPPORTED;
-    }
-    return check_launch("gemm_dw_pair");
+    return with_cfg<kNumCfgs>(cfg, [&](auto ci) -> int {
+        if constexpr (dw2_ok(decltype(ci)::value)) {
+            constexpr PipeCfg c = kCfgs[decltype(ci)::value];
+            launch_lds<gemm_dw2_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, c.il, ERGM_EPI_NONE, c.mf>, c.lds_bytes()>(
+                dim3(nb), dim3(c.threads()), s, g);
+            return check_launch("gemm_dw_pair");
+        } else {
+            return ERGM_EUNSUPPORTED;  // refused above already
+        }
+    });
 }
 }  // namespace ergm

@@ -92,12 +92,13 @@ def test_gemm_split_k(gpu, split):
 @pytest.mark.parametrize("M,N,K,split,cfg", [(768, 2304, 2048, 1, -1), (768, 768, 4096, 0, -1),
                                                (200, 136, 1000, 1, -1), (256, 512, 2048, 3, -1),
                                                (256, 512, 1024, 1, 0), (256, 512, 1024, 2, 2),
-                                               (256, 512, 1024, 1, 16)])
+                                               (256, 512, 1024, 1, 16), (256, 512, 1024, 1, 38),
+                                               (256, 512, 1024, 2, 38), (256, 512, 1024, 1, 33)])
 def test_gemm_bias_grad(gpu, M, N, K, split, cfg):
     """Weight gradient + its Conv1D bias gradient in one GEMM (ergm_gemm_desc.bias_grad): dW = Xᵀ·dY and
     db = Σ_t dY[t] (the in-kernel column sums of the pipelined kernels, their split-K partials, and the
-    column-sum pass of the kernels without it: register-staged for K % 64 != 0, warp-specialised cfg 16),
-    against fp64; bitwise reproducible."""
+    column-sum pass of the kernels without it: register-staged for K % 64 != 0, warp-specialised cfg 16,
+    32x32-MFMA cfg 38 unsplit and split, intra-workgroup split-K cfg 33), against fp64; bitwise reproducible."""
     g = torch.Generator(device="cpu").manual_seed(M + N + K)
     X = (torch.randn(K, M, generator=g) * 0.5).to(gpu, torch.bfloat16)   # [tokens][in]  (KM)
     dY = (torch.randn(K, N, generator=g) * 0.5).to(gpu, torch.bfloat16)  # [tokens][out] (KN)
