@@ -13,7 +13,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libergm_hip.so")
 
-ABI_VERSION = 13  # ERGM_ABI_VERSION of include/ergm_hip.h this binding matches
+ABI_VERSION = 14  # ERGM_ABI_VERSION of include/ergm_hip.h this binding matches
 ERGM_OK, ERGM_EINVAL, ERGM_EUNSUPPORTED, ERGM_EHIP = 0, -1, -2, -3
 F32, BF16 = 0, 1
 MK, KM = 0, 1
@@ -78,6 +78,8 @@ _SIGS = {
     "ergm_gemm_trace": (i32, [i32, vp, i32]),
     "ergm_gemm_workspace_size": (sz, [C.POINTER(GemmDesc)]),
     "ergm_gemm": (i32, [C.POINTER(GemmDesc), vp, vp, vp, vp, sz, vp]),
+    "ergm_gemm_plan": (i32, [C.POINTER(GemmDesc), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "ergm_gemm_cfg_count": (i32, []),
     "ergm_gemm_f8": (i32, [C.POINTER(GemmDesc), vp, vp, vp, vp, vp, vp]),
     "ergm_gemm_f8_tune": (i32, [i32]),
     "ergm_gemm_f8_set_override": (i32, [i32, i32, i32, i32]),

@@ -1223,10 +1223,12 @@ struct GemmPlan {
 
 static long tiles_of(int M, int N, int bm, int bn) { return (long)cdiv(M, bm) * cdiv(N, bn); }
 
-// Split-K workspace of a planned GEMM: the f32 slabs [split][M][N], then the bias gradient's partials [split][N].
+// Split-K workspace of a planned GEMM: the f32 slabs [split][M][N], then the bias gradient's partials [split][N]
+// where the kernel sums them (make_args sets GemmArgs::colsum by the same rule); the column-sum pass needs none.
 static size_t split_ws_bytes(const ergm_gemm_desc* d, const GemmPlan& p) {
     if (p.split <= 1) return 0;
-    return (size_t)p.split * d->M * d->N * sizeof(float) + (d->bias_grad ? (size_t)p.split * d->N * sizeof(float) : 0);
+    const bool cs_in = d->bias_grad && p.cfg >= 0 && kCfgs[p.cfg].has_colsum();
+    return (size_t)p.split * d->M * d->N * sizeof(float) + (cs_in ? (size_t)p.split * d->N * sizeof(float) : 0);
 }
 
 // Layout / epilogue / output-type combinations instantiated for the pipelined kernels (the ones the
@@ -1807,16 +1809,15 @@ static GemmArgs make_args(const ergm_gemm_desc* d, const void* A, const void* B,
 }  // namespace ergm
 
 namespace ergm {
-// Argument checks of ergm_gemm (also applied to each problem of a grouped launch).
-static int validate_desc(const ergm_gemm_desc* d, const void* A, const void* B, const void* C) {
-    ERGM_CHECK_ARG(d && A && B && C, "ergm_gemm: null argument");
+// The checks of a descriptor's own fields: shape, leading dimensions, layouts, output type and epilogue.  No operand
+// pointer is looked at, so the planning query (ergm_gemm_plan) applies them too.
+static int validate_fields(const ergm_gemm_desc* d) {
     ERGM_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "ergm_gemm: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
     // k-contiguous operands are read in 8-element chunks along K; with both operands k-major (rows = k,
     // the weight-gradient layout) any K works
     ERGM_CHECK_ARG(d->K % 8 == 0 || (d->a_layout == ERGM_KM && d->b_layout == ERGM_KN),
                    "ergm_gemm: K=%d must be a multiple of 8 unless a_layout = KM and b_layout = KN", d->K);
     ERGM_CHECK_ARG(d->lda % 8 == 0 && d->ldb % 8 == 0, "ergm_gemm: lda/ldb must be multiples of 8 elements");
-    ERGM_CHECK_ARG(aligned16(A) && aligned16(B), "ergm_gemm: A/B must be 16-byte aligned");
     ERGM_CHECK_ARG(d->a_layout == ERGM_MK || d->a_layout == ERGM_KM, "ergm_gemm: bad a_layout");
     ERGM_CHECK_ARG(d->b_layout == ERGM_NK || d->b_layout == ERGM_KN, "ergm_gemm: bad b_layout");
     ERGM_CHECK_ARG(d->a_layout == ERGM_MK ? d->lda >= d->K : d->lda >= d->M, "ergm_gemm: lda too small");
@@ -1841,7 +1842,14 @@ static int validate_desc(const ergm_gemm_desc* d, const void* A, const void* B, 
     ERGM_CHECK_ARG(!(d->m_count_dev || d->k_count_dev || d->row_map) ||
                        (d->b_layout == ERGM_KN && e == ERGM_EPI_NONE && d->c_dtype == ERGM_F32 && !d->bias_grad),
                    "ergm_gemm: m_count_dev / k_count_dev / row_map need b_layout KN, epilogue NONE, f32 C, no bias_grad");
+    return ERGM_OK;
+}
 
+// Argument checks of ergm_gemm (also applied to each problem of a grouped launch).
+static int validate_desc(const ergm_gemm_desc* d, const void* A, const void* B, const void* C) {
+    ERGM_CHECK_ARG(d && A && B && C, "ergm_gemm: null argument");
+    ERGM_TRY(validate_fields(d));
+    ERGM_CHECK_ARG(aligned16(A) && aligned16(B), "ergm_gemm: A/B must be 16-byte aligned");
     return ERGM_OK;
 }
 }  // namespace ergm
@@ -1892,6 +1900,23 @@ extern "C" int ergm_gemm(const ergm_gemm_desc* d, const void* A, const void* B, 
                            d->alpha_dev, d->bias_grad);
     return check_launch("ergm_gemm");
 }
+
+// What ergm_gemm would run for `d` now: plan_gemm / plan_dyn and make_args as ergm_gemm calls them (the forced
+// configuration of this thread and the override tables included), on a descriptor checked without its operands.
+// Host only: no launch, no HIP call, nothing traced.
+extern "C" int ergm_gemm_plan(const ergm_gemm_desc* d, int* cfg, int* split, int* flags) {
+    ERGM_CHECK_ARG(d && cfg && split && flags, "ergm_gemm_plan: null argument");
+    ERGM_TRY(validate_fields(d));
+    const bool dyn = is_dyn(d);
+    const GemmPlan p = dyn ? plan_dyn(d) : plan_gemm(d);
+    const GemmArgs a = make_args(d, nullptr, nullptr, nullptr, p);
+    *cfg = p.cfg;
+    *split = p.split;
+    *flags = (a.colsum ? 1 : 0) | (a.xcd_split ? 2 : 0) | (dyn ? 4 : 0);
+    return ERGM_OK;
+}
+
+extern "C" int ergm_gemm_cfg_count(void) { return kNumCfgs; }
 
 namespace ergm {
 // Two weight-gradient GEMMs (a_layout KM, b_layout KN, epilogue NONE, f32 C) in one launch when both plan

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ERGM_ABI_VERSION 13  /* 13: ergm_attn_decode, ergm_embed_rows, ergm_topp_sample (batched generation) */
+#define ERGM_ABI_VERSION 14  /* 14: ergm_gemm_plan, ergm_gemm_cfg_count (the planning query) */
 
 typedef enum {
     ERGM_OK = 0,
@@ -156,6 +156,16 @@ int ergm_gemm_trace(int on, int* shapes, int max_shapes);
 size_t ergm_gemm_workspace_size(const ergm_gemm_desc* desc);
 int ergm_gemm(const ergm_gemm_desc* desc, const void* A, const void* B, void* C, void* workspace,
               size_t ws_bytes, void* stream);
+/* Planning query (ABI 14, host only: works without a GPU, launches nothing, leaves the shape trace as it is).
+ * Reports what ergm_gemm would run for `desc` right now, the calling thread's ergm_gemm_tune setting and the
+ * override tables included: *cfg = the index into kCfgs, or -1 for the register-staged kernel; *split = the
+ * effective split-K count after rounding the slices to whole 64-deep K steps; *flags bit 0 = the bias gradient
+ * is summed inside the GEMM kernel (else by the column-sum pass behind it), bit 1 = one K slice per XCD, bit 2 =
+ * the path with device-side extents.  The descriptor's shape, layout and epilogue fields are checked as ergm_gemm
+ * checks them (ERGM_EINVAL); no operand pointer is needed, and the device pointers inside `desc` are only tested for NULL.
+ * ergm_gemm_cfg_count returns the number of entries of kCfgs (the bound of ergm_gemm_tune's cfg).             */
+int ergm_gemm_plan(const ergm_gemm_desc* desc, int* cfg, int* split, int* flags);
+int ergm_gemm_cfg_count(void);
 
 /* fp8 GEMM (config 5's forward Conv1D GEMMs; build-side, the reference is fp32):
  *   C = epilogue(alpha · a_scale[m] · b_scale[n] · Σ_k A[m][k]·B[n][k])

@@ -22,7 +22,7 @@ def test_new_exports_declared_bound_and_present():
     for name in NEW:
         assert re.search(r"\b%s\s*\(" % name, src), name
         assert name in L.EXPORTED and hasattr(lib, name), name
-    assert L.ABI_VERSION == 13 and re.search(r"#define\s+ERGM_ABI_VERSION\s+13\b", src)
+    assert L.ABI_VERSION == 14 and re.search(r"#define\s+ERGM_ABI_VERSION\s+14\b", src)
 
 
 def _buf(nbytes=256):
