@@ -69,6 +69,20 @@ class ModelParams(C.Structure):
                 ("g_aproj_w", C.c_void_p), ("g_aproj_b", C.c_void_p), ("capkv_w", C.c_void_p)]
 
 
+class LinearRowsDesc(C.Structure):
+    """ergm_linear_rows_desc (ergm_hip.h)."""
+    _fields_ = [("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("lda", C.c_int), ("ldw", C.c_int), ("ldc", C.c_int),
+                ("w_layout", C.c_int), ("epilogue", C.c_int), ("bias", C.c_void_p), ("aux", C.c_void_p),
+                ("ld_aux", C.c_int), ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_eps", C.c_float)]
+
+
+class DecodeDims(C.Structure):
+    """ergm_decode_dims (ergm_hip.h)."""
+    _fields_ = [("vocab", C.c_int), ("vocab_pad", C.c_int), ("n_embd", C.c_int), ("n_layer", C.c_int),
+                ("n_head", C.c_int), ("n_inner", C.c_int), ("n_positions", C.c_int), ("max_batch", C.c_int),
+                ("max_len", C.c_int), ("cap_max", C.c_int), ("eps", C.c_float)]
+
+
 vp, i32, i64, f32, f64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 _SIGS = {
     "ergm_version": (i32, []),
@@ -95,6 +109,15 @@ _SIGS = {
     "ergm_embed_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ergm_topp_sample": (i32, [vp, i32, i32, i32, f32, C.c_uint64, C.c_uint32, vp, i64, vp, vp, vp, vp]),
     "ergm_attn_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp] + [i32] * 13 + [vp, vp, vp]),
+    "ergm_linear_rows": (i32, [C.POINTER(LinearRowsDesc), vp, vp, vp, vp]),
+    "ergm_decode_workspace_size": (sz, [C.POINTER(DecodeDims)]),
+    "ergm_decode_create": (i32, [C.POINTER(DecodeDims), C.POINTER(ModelParams), vp, sz, C.POINTER(vp)]),
+    "ergm_decode_destroy": (i32, [vp]),
+    "ergm_decode_bind": (i32, [vp, i32, i32, C.POINTER(vp), C.POINTER(vp), i32, vp, vp, vp, vp]),
+    "ergm_decode_set_engine": (i32, [vp, i32]),
+    "ergm_decode_step": (i32, [vp, vp, vp, vp]),
+    "ergm_decode_run": (i32, [vp, i32, i32, f32, C.c_uint64, i64, i64, vp, vp]),
+    "ergm_decode_launches": (i32, [vp, i32]),
     "ergm_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "ergm_layernorm_bwd_workspace_size": (sz, [i32, i32]),
     "ergm_layernorm_bwd": (i32, [vp] * 10 + [sz, i32, i32, vp, vp]),

@@ -372,6 +372,28 @@ __global__ __launch_bounds__(TP_THREADS) void topp_sample_kernel(const float* __
     }
 }
 
+// ---- the decode executor's integer helpers (decode_exec.cpp) -------------------------------------------
+// lens[b] += !finished[b]: the sequences that have not drawn eos advance by the token just appended
+__global__ void lens_advance_kernel(int* __restrict__ lens, const uint8_t* __restrict__ finished, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) lens[b] += finished[b] == 0 ? 1 : 0;
+}
+__global__ void fill_i64_kernel(int64_t* __restrict__ p, int64_t v, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+int decode_lens_advance(int* lens, const uint8_t* finished, int B, hipStream_t s) {
+    ERGM_LAUNCH(lens_advance_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, lens, finished, B);
+    return check_launch("decode_lens_advance");
+}
+int decode_fill_i64(int64_t* p, int64_t v, int n, hipStream_t s) {
+    ERGM_LAUNCH(fill_i64_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, p, v, n);
+    return check_launch("decode_fill_i64");
+}
+// kernel launches of one ergm_attn_decode call with splits = 0
+int attn_decode_launches(int B, int H, int max_len) { return decode_auto_splits(B, H, max_len) > 1 ? 2 : 1; }
+
 }  // namespace ergm
 
 using namespace ergm;

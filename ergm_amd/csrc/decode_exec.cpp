@@ -1,0 +1,355 @@
+// Native decode executor (ergm_hip.h, ergm_decode_*): BatchedGenerator.step and the sampling loop of
+// BatchedGenerator.generate (ergm_amd/generate.py) as launch sequences on the caller's one stream.
+//
+// The step is written once (walk): every kernel goes through Walk::on, which counts the launch and, in a dry walk,
+// returns before calling anything, so ergm_decode_launches reports what ergm_decode_step enqueues.  Engine 0 calls
+// the C-ABI entry points the Python path calls, with its arguments; engine 1 puts ergm_linear_rows in the
+// place of each LayerNorm + GEMM pair and each plain GEMM of the blocks.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "common.h"
+
+namespace ergm {
+int decode_lens_advance(int* lens, const uint8_t* finished, int B, hipStream_t s);
+int decode_fill_i64(int64_t* p, int64_t v, int n, hipStream_t s);
+int attn_decode_launches(int B, int H, int max_len);
+}  // namespace ergm
+
+using namespace ergm;
+
+struct ergm_decode_plan {
+    ergm_decode_dims d;
+    ergm_model_params p;
+    // workspace
+    float* h;        // [max_batch][E] the residual stream of the step
+    __bf16* x;       // [max_batch][E] LayerNorm output (engine 0, and the head of engine 1)
+    __bf16* qkv;     // [max_batch][3E]
+    __bf16* att;     // [max_batch][E] attention output
+    __bf16* q;       // [max_batch][E] cross-attention query
+    __bf16* pre;     // [max_batch][F] gelu' (engine 0: the Python path's aux_out)
+    __bf16* act;     // [max_batch][F]
+    float* mean;     // [max_batch]
+    float* rstd;
+    int64_t* tt;     // [max_batch] ergm_decode_run's token types
+    void* attn_ws;
+    size_t attn_ws_bytes;
+    void* gemm_ws;
+    size_t gemm_ws_bytes;
+    // bound state
+    bool bound;
+    int B, n_max, Sc, engine;
+    int head_lr;     // measurement switch ERGM_DECODE_HEAD (engine 1 only): 0 = ergm_gemm, 1 = lr, 2 = ln
+    std::vector<void*> kv, xkv;
+    int* lens;
+    const int* cap_lens;
+    uint8_t* finished;
+    float* logits;
+};
+
+namespace {
+
+constexpr int kEngines = 2;
+
+size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+bool dims_ok(const ergm_decode_dims& d) {
+    return d.n_embd > 0 && d.n_head > 0 && d.n_embd == 64 * d.n_head && d.n_embd <= 1024 && d.n_inner > 0 &&
+           d.n_inner % 64 == 0 && d.vocab > 0 && d.vocab_pad >= d.vocab && d.vocab_pad % 64 == 0 && d.n_layer > 0 &&
+           d.max_batch > 0 && d.max_len > 0 && d.max_len <= d.n_positions && d.cap_max > 0;
+}
+
+ergm_gemm_desc gemm_desc(int M, int N, int K, int b_layout, int c_dtype, int epi, const float* bias, const void* aux,
+                         void* aux_out, int ldc) {
+    ergm_gemm_desc g{};
+    g.M = M, g.N = N, g.K = K;
+    g.lda = K, g.ldb = b_layout == ERGM_KN ? N : K, g.ldc = ldc;
+    g.a_layout = ERGM_MK, g.b_layout = b_layout, g.c_dtype = c_dtype, g.epilogue = epi;
+    g.alpha = 1.0f;
+    g.bias = bias;
+    g.aux = aux, g.ld_aux = aux ? ldc : 0;
+    g.aux_out = aux_out, g.ld_aux_out = aux_out ? N : 0;
+    return g;
+}
+
+// The largest split-K workspace of the step's GEMMs over every batch size the plan can be bound to.
+size_t gemm_ws_need(const ergm_decode_dims& d) {
+    const int E = d.n_embd, F = d.n_inner;
+    const int shapes[5][3] = {{3 * E, E, ERGM_KN}, {E, E, ERGM_KN}, {F, E, ERGM_KN}, {E, F, ERGM_KN}, {d.vocab_pad, E, ERGM_NK}};
+    size_t need = 0;
+    for (int M = 1; M <= d.max_batch; ++M)
+        for (const auto& s : shapes) {
+            const ergm_gemm_desc g = gemm_desc(M, s[0], s[1], s[2], ERGM_F32, ERGM_EPI_NONE, nullptr, nullptr, nullptr, s[0]);
+            need = std::max(need, ergm_gemm_workspace_size(&g));
+        }
+    return need;
+}
+
+// Carves the workspace; base == nullptr only sizes it.
+size_t carve(ergm_decode_plan* P, char* base) {
+    const ergm_decode_dims& d = P->d;
+    const size_t mb = d.max_batch, E = d.n_embd, F = d.n_inner;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* p = base ? base + off : nullptr;
+        off += al256(bytes);
+        return p;
+    };
+    P->h = reinterpret_cast<float*>(take(mb * E * 4));
+    P->x = reinterpret_cast<__bf16*>(take(mb * E * 2));
+    P->qkv = reinterpret_cast<__bf16*>(take(mb * 3 * E * 2));
+    P->att = reinterpret_cast<__bf16*>(take(mb * E * 2));
+    P->q = reinterpret_cast<__bf16*>(take(mb * E * 2));
+    P->pre = reinterpret_cast<__bf16*>(take(mb * F * 2));
+    P->act = reinterpret_cast<__bf16*>(take(mb * F * 2));
+    P->mean = reinterpret_cast<float*>(take(mb * 4));
+    P->rstd = reinterpret_cast<float*>(take(mb * 4));
+    P->tt = reinterpret_cast<int64_t*>(take(mb * 8));
+    P->attn_ws_bytes = std::max<size_t>(16, ergm_attn_decode_workspace_size(d.max_batch, d.n_head, std::max(d.max_len, d.cap_max)));
+    P->attn_ws = take(P->attn_ws_bytes);
+    P->gemm_ws_bytes = std::max<size_t>(16, gemm_ws_need(d));
+    P->gemm_ws = take(P->gemm_ws_bytes);
+    return off;
+}
+
+struct Walk {
+    bool dry;
+    int count = 0;
+    hipStream_t s = nullptr;
+    // counts `launches` kernels; true when the caller should enqueue them
+    bool on(int launches = 1) {
+        count += launches;
+        return !dry;
+    }
+};
+
+const float* lf(const ergm_decode_plan* P, int l, int t) {
+    return P->p.layer_f32 + (int64_t)l * P->p.layer_stride + P->p.layer_off[t];
+}
+const __bf16* lb(const ergm_decode_plan* P, int l, int t) {
+    return reinterpret_cast<const __bf16*>(P->p.layer_b16) + (int64_t)l * P->p.layer_stride + P->p.layer_off[t];
+}
+
+int ln(const ergm_decode_plan* P, Walk& w, int B, const float* g, const float* b) {
+    if (!w.on()) return ERGM_OK;
+    return ergm_layernorm_fwd(P->h, g, b, P->x, P->mean, P->rstd, B, P->d.n_embd, P->d.eps, w.s);
+}
+
+// ergm_gemm as ops.gemm calls it (split_k = 0, the workspace of its own query)
+int gemm(const ergm_decode_plan* P, Walk& w, int B, int N, int K, const void* A, const void* W, int b_layout, void* C,
+         int c_dtype, int epi, const float* bias, const void* aux, void* aux_out, int ldc) {
+    const ergm_gemm_desc g = gemm_desc(B, N, K, b_layout, c_dtype, epi, bias, aux, aux_out, ldc);
+    int cfg = 0, split = 1, flags = 0;
+    ERGM_TRY(ergm_gemm_plan(&g, &cfg, &split, &flags));
+    if (!w.on(split > 1 ? 2 : 1)) return ERGM_OK;
+    const size_t need = ergm_gemm_workspace_size(&g);
+    ERGM_CHECK_ARG(need <= P->gemm_ws_bytes, "decode_step: GEMM workspace %zu > %zu bytes (a GEMM override set after the plan)",
+                   need, P->gemm_ws_bytes);
+    return ergm_gemm(&g, A, W, C, P->gemm_ws, need, w.s);
+}
+
+int linear(const ergm_decode_plan* P, Walk& w, int B, int N, int K, const void* A, const float* gamma, const float* beta,
+           const void* W, int w_layout, void* C, int epi, const float* bias, const float* aux, int ldc) {
+    if (!w.on()) return ERGM_OK;
+    ergm_linear_rows_desc g{};
+    g.M = B, g.N = N, g.K = K;
+    g.lda = K, g.ldw = w_layout == ERGM_KN ? N : K, g.ldc = ldc;
+    g.w_layout = w_layout, g.epilogue = epi;
+    g.bias = bias;
+    g.aux = aux, g.ld_aux = aux ? ldc : 0;
+    g.ln_gamma = gamma, g.ln_beta = beta, g.ln_eps = P->d.eps;
+    return ergm_linear_rows(&g, A, W, C, w.s);
+}
+
+// LayerNorm(h; ln tensors t_ln, t_ln+1) -> Conv1D (weight t_w, bias t_w+1) of block l, N columns, into bf16 C
+int ln_linear(const ergm_decode_plan* P, Walk& w, int B, int l, int t_ln, int t_w, int N, void* C, int epi) {
+    const int E = P->d.n_embd;
+    if (P->engine == 0) {
+        ERGM_TRY(ln(P, w, B, lf(P, l, t_ln), lf(P, l, t_ln + 1)));
+        void* aux_out = epi == ERGM_EPI_BIAS_GELU ? P->pre : nullptr;
+        return gemm(P, w, B, N, E, P->x, lb(P, l, t_w), ERGM_KN, C, ERGM_BF16, epi, lf(P, l, t_w + 1), nullptr, aux_out, N);
+    }
+    return linear(P, w, B, N, E, P->h, lf(P, l, t_ln), lf(P, l, t_ln + 1), lb(P, l, t_w), ERGM_KN, C, epi, lf(P, l, t_w + 1),
+                  nullptr, N);
+}
+
+// h += A·W + bias (weight t_w of block l, K rows)
+int proj_resid(const ergm_decode_plan* P, Walk& w, int B, int l, int t_w, int K, const void* A) {
+    const int E = P->d.n_embd;
+    if (P->engine == 0)
+        return gemm(P, w, B, E, K, A, lb(P, l, t_w), ERGM_KN, P->h, ERGM_F32, ERGM_EPI_BIAS_RESID, lf(P, l, t_w + 1), P->h,
+                    nullptr, E);
+    return linear(P, w, B, E, K, A, nullptr, nullptr, lb(P, l, t_w), ERGM_KN, P->h, ERGM_EPI_BIAS_RESID, lf(P, l, t_w + 1),
+                  P->h, E);
+}
+
+int attn(const ergm_decode_plan* P, Walk& w, int B, const __bf16* qkv, int ld_qkv, void* cache, int rows, const int* lens,
+         int append) {
+    const ergm_decode_dims& d = P->d;
+    if (!w.on(attn_decode_launches(B, d.n_head, rows))) return ERGM_OK;
+    __bf16* k = reinterpret_cast<__bf16*>(cache);
+    return ergm_attn_decode(qkv, ld_qkv, k, k + d.n_embd, (int64_t)rows * 2 * d.n_embd, 2 * d.n_embd, lens, B, d.n_head, rows,
+                            append, 0, P->att, d.n_embd, P->attn_ws, P->attn_ws_bytes, w.s);
+}
+
+// One decode step for B sequences; a dry walk (w.dry) only counts.
+int walk(const ergm_decode_plan* P, Walk& w, int B, const int64_t* tokens, const int64_t* tt) {
+    const ergm_decode_dims& d = P->d;
+    const int E = d.n_embd, F = d.n_inner;
+    if (w.on())
+        ERGM_TRY(ergm_embed_rows(tokens, tt, P->lens, P->p.wte, P->p.wpe, P->h, B, E, d.vocab_pad, d.n_positions, w.s));
+    for (int l = 0; l < d.n_layer; ++l) {
+        ERGM_TRY(ln_linear(P, w, B, l, ERGM_T_LN1_W, ERGM_T_ATTN_W, 3 * E, P->qkv, ERGM_EPI_BIAS));
+        ERGM_TRY(attn(P, w, B, P->qkv, 3 * E, w.dry ? nullptr : P->kv[l], d.max_len, P->lens, 1));
+        ERGM_TRY(proj_resid(P, w, B, l, ERGM_T_APROJ_W, E, P->att));
+        ERGM_TRY(ln_linear(P, w, B, l, ERGM_T_LNX_W, ERGM_T_XQ_W, E, P->q, ERGM_EPI_BIAS));
+        ERGM_TRY(attn(P, w, B, P->q, E, w.dry ? nullptr : P->xkv[l], P->bound ? P->Sc : d.cap_max, P->cap_lens, 0));
+        ERGM_TRY(proj_resid(P, w, B, l, ERGM_T_XPROJ_W, E, P->att));
+        ERGM_TRY(ln_linear(P, w, B, l, ERGM_T_LN2_W, ERGM_T_FC_W, F, P->act, ERGM_EPI_BIAS_GELU));
+        ERGM_TRY(proj_resid(P, w, B, l, ERGM_T_MPROJ_W, F, P->act));
+    }
+    // The head stays ln_f + ergm_gemm on both engines: at N = vocab_pad ergm_gemm has hundreds of workgroups already and
+    // measured 19 us against ergm_linear_rows' 41 us at B = 32 (139 us with the LayerNorm in the prologue, every strip
+    // re-reading the rows).  ERGM_DECODE_HEAD=lr / ln, read when the plan is created, puts engine 1's head
+    // on ergm_linear_rows behind ergm_layernorm_fwd / with the prologue, to repeat that measurement.
+    const int head = P->engine == 1 ? P->head_lr : 0;
+    if (head == 2) {
+        ERGM_TRY(linear(P, w, B, d.vocab_pad, E, P->h, P->p.ln_f_w, P->p.ln_f_b, P->p.wte_b, ERGM_NK, P->logits, ERGM_EPI_NONE,
+                        nullptr, nullptr, d.vocab_pad));
+    } else {
+        ERGM_TRY(ln(P, w, B, P->p.ln_f_w, P->p.ln_f_b));
+        if (head == 0)
+            ERGM_TRY(gemm(P, w, B, d.vocab_pad, E, P->x, P->p.wte_b, ERGM_NK, P->logits, ERGM_F32, ERGM_EPI_NONE, nullptr,
+                          nullptr, nullptr, d.vocab_pad));
+        else
+            ERGM_TRY(linear(P, w, B, d.vocab_pad, E, P->x, nullptr, nullptr, P->p.wte_b, ERGM_NK, P->logits, ERGM_EPI_NONE,
+                            nullptr, nullptr, d.vocab_pad));
+    }
+    if (w.on()) ERGM_TRY(decode_lens_advance(P->lens, P->finished, B, w.s));
+    return ERGM_OK;
+}
+
+int step_ready(const ergm_decode_plan* P, int steps, const char* what) {
+    ERGM_CHECK_ARG(P, "%s: null plan", what);
+    ERGM_CHECK_ARG(P->bound, "%s: no state bound (ergm_decode_bind after the prefill)", what);
+    ERGM_CHECK_ARG(P->n_max + steps <= P->d.max_len, "%s: KV cache full (%d rows used, %d step(s), max_len %d)", what,
+                   P->n_max, steps, P->d.max_len);
+    return ERGM_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ergm_decode_workspace_size(const ergm_decode_dims* dims) {
+    if (!dims || !dims_ok(*dims)) return 0;
+    ergm_decode_plan P{};
+    P.d = *dims;
+    return carve(&P, nullptr);
+}
+
+extern "C" int ergm_decode_create(const ergm_decode_dims* dims, const ergm_model_params* params, void* ws, size_t ws_bytes,
+                                  ergm_decode_plan** out) {
+    ERGM_CHECK_ARG(dims && params && ws && out, "decode_create: null argument");
+    const ergm_decode_dims& d = *dims;
+    ERGM_CHECK_ARG(d.n_embd > 0 && d.n_head > 0 && d.n_embd == 64 * d.n_head,
+                   "decode_create: head_dim must be 64 (n_embd=%d n_head=%d)", d.n_embd, d.n_head);
+    ERGM_CHECK_ARG(dims_ok(d), "decode_create: unsupported dimensions (n_embd <= 1024, n_inner %% 64, vocab_pad %% 64, "
+                               "1 <= max_len <= n_positions, max_batch, cap_max, n_layer >= 1)");
+    ERGM_CHECK_ARG(params->wte && params->wte_b && params->wpe && params->ln_f_w && params->ln_f_b && params->layer_f32 &&
+                       params->layer_b16,
+                   "decode_create: null forward parameter");
+    ERGM_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "decode_create: workspace must be 256-byte aligned");
+    const size_t need = ergm_decode_workspace_size(dims);
+    ERGM_CHECK_ARG(ws_bytes >= need, "decode_create: workspace %zu < %zu bytes", ws_bytes, need);
+    auto* P = new (std::nothrow) ergm_decode_plan();
+    if (!P) return fail(ERGM_EINVAL, "decode_create: out of host memory");
+    P->d = d;
+    P->p = *params;
+    carve(P, reinterpret_cast<char*>(ws));
+    P->bound = false;
+    P->B = P->n_max = P->Sc = P->engine = 0;
+    P->head_lr = 0;
+    if (const char* e = getenv("ERGM_DECODE_HEAD")) P->head_lr = !strcmp(e, "lr") ? 1 : (!strcmp(e, "ln") ? 2 : 0);
+    P->lens = nullptr;
+    P->cap_lens = nullptr;
+    P->finished = nullptr;
+    P->logits = nullptr;
+    *out = P;
+    return ERGM_OK;
+}
+
+extern "C" int ergm_decode_destroy(ergm_decode_plan* P) {
+    delete P;
+    return ERGM_OK;
+}
+
+extern "C" int ergm_decode_bind(ergm_decode_plan* P, int B, int n_max, void* const* kv, void* const* xkv, int Sc, int* lens,
+                                const int* cap_lens, uint8_t* finished, float* logits) {
+    ERGM_CHECK_ARG(P && kv && xkv && lens && cap_lens && finished && logits, "decode_bind: null argument");
+    ERGM_CHECK_ARG(B >= 1 && B <= P->d.max_batch, "decode_bind: B %d outside [1, max_batch %d]", B, P->d.max_batch);
+    ERGM_CHECK_ARG(n_max >= 1 && n_max <= P->d.max_len, "decode_bind: n_max %d outside [1, max_len %d]", n_max, P->d.max_len);
+    ERGM_CHECK_ARG(Sc >= 1 && Sc <= P->d.cap_max, "decode_bind: Sc %d outside [1, cap_max %d]", Sc, P->d.cap_max);
+    for (int l = 0; l < P->d.n_layer; ++l)
+        ERGM_CHECK_ARG(kv[l] && xkv[l] && aligned16(kv[l]) && aligned16(xkv[l]),
+                       "decode_bind: layer %d cache pointer null or not 16-byte aligned", l);
+    ERGM_CHECK_ARG(aligned16(logits), "decode_bind: logits must be 16-byte aligned");
+    P->kv.assign(kv, kv + P->d.n_layer);
+    P->xkv.assign(xkv, xkv + P->d.n_layer);
+    P->B = B, P->n_max = n_max, P->Sc = Sc;
+    P->lens = lens, P->cap_lens = cap_lens, P->finished = finished, P->logits = logits;
+    P->bound = true;
+    return ERGM_OK;
+}
+
+extern "C" int ergm_decode_set_engine(ergm_decode_plan* P, int engine) {
+    ERGM_CHECK_ARG(P && engine >= 0 && engine < kEngines, "decode_set_engine: engine %d outside [0, %d)", engine, kEngines);
+    P->engine = engine;
+    return ERGM_OK;
+}
+
+extern "C" int ergm_decode_step(ergm_decode_plan* P, const int64_t* tokens, const int64_t* token_types, void* stream) {
+    ERGM_TRY(step_ready(P, 1, "decode_step"));
+    ERGM_CHECK_ARG(tokens, "decode_step: null tokens");
+    Walk w{false};
+    w.s = as_stream(stream);
+    ERGM_TRY(walk(P, w, P->B, tokens, token_types));
+    P->n_max += 1;
+    return ERGM_OK;
+}
+
+extern "C" int ergm_decode_run(ergm_decode_plan* P, int first, int n, float top_p, uint64_t seed, int64_t eos_id,
+                               int64_t sp2_id, int64_t* tokens_out, void* stream) {
+    ERGM_CHECK_ARG(P, "decode_run: null plan");
+    ERGM_CHECK_ARG(n >= 1 && first >= 0 && first <= INT32_MAX - n, "decode_run: bad range first %d n %d", first, n);
+    ERGM_TRY(step_ready(P, n - (first == 0 ? 1 : 0), "decode_run"));
+    ERGM_CHECK_ARG(tokens_out, "decode_run: null tokens_out");
+    ERGM_CHECK_ARG(top_p == top_p, "decode_run: top_p is NaN");
+    hipStream_t s = as_stream(stream);
+    const int B = P->B;
+    ERGM_TRY(decode_fill_i64(P->tt, sp2_id, B, s));
+    for (int i = first; i < first + n; ++i) {
+        if (i > 0) {
+            Walk w{false};
+            w.s = s;
+            ERGM_TRY(walk(P, w, B, tokens_out + (size_t)(i - 1) * B, P->tt));
+            P->n_max += 1;  // per step: after a launch failure part-way n_max counts the steps that were enqueued; the
+                            // caller then rebinds (ergm_decode_bind sets n_max again) before it goes on
+        }
+        ERGM_TRY(ergm_topp_sample(P->logits, P->d.vocab_pad, B, P->d.vocab, top_p, seed, (uint32_t)i, P->finished, eos_id,
+                                  tokens_out + (size_t)i * B, nullptr, nullptr, s));
+    }
+    return ERGM_OK;
+}
+
+extern "C" int ergm_decode_launches(const ergm_decode_plan* P, int engine) {
+    ERGM_CHECK_ARG(P && engine >= 0 && engine < kEngines, "decode_launches: bad plan or engine %d", engine);
+    ergm_decode_plan Q = *P;
+    Q.engine = engine;
+    Walk w{true};
+    ERGM_TRY(walk(&Q, w, P->bound ? P->B : P->d.max_batch, nullptr, nullptr));
+    return w.count;
+}

@@ -22,6 +22,7 @@ for the whole batch without a sort or a host round trip.  ``KVCacheGenerator`` i
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import List, Optional
 
 import torch
@@ -165,9 +166,21 @@ class BatchedGenerator:
 
     ``prefill`` encodes the right-padded prompts with the training kernels (causal attention hides the padding
     from the real rows; the padded rows' K/V land in cache rows >= lens[b], which decode overwrites before it
-    reads them); ``step`` appends one token per sequence; ``generate`` is nucleus sampling of the whole batch."""
+    reads them); ``step`` appends one token per sequence; ``generate`` is nucleus sampling of the whole batch.
 
-    def __init__(self, model, max_batch: int, max_len: int = 1024):
+    ``engine``: "python" (default) drives every kernel of a step from Python; "native" hands the step and the
+    sampling loop to the library's decode executor (``ergm_decode_*``), which enqueues the same kernels with the same
+    arguments (bitwise the Python path); "fused" is the executor on ``ergm_linear_rows``, one launch per LayerNorm +
+    GEMM pair.  The prefill is the Python path in every case and ends by binding its caches to the executor."""
+
+    ENGINES = {"python": None, "native": 0, "fused": 1}   # the executor's engine numbers
+
+    def __init__(self, model, max_batch: int, max_len: int = 1024, engine: str = "python"):
+        if engine not in self.ENGINES:
+            raise ValueError(f"engine {engine!r} is not one of {sorted(self.ENGINES)}")
+        self.engine = engine
+        self._plan = self._plan_ws = self._plan_params = None
+        self._cap_max = 0
         cfg = model.config
         if max_len > cfg.n_positions:
             raise ValueError(f"max_len {max_len} > n_positions {cfg.n_positions}")
@@ -190,6 +203,56 @@ class BatchedGenerator:
 
     # parameter views and LayerNorm as the single-sequence generator has them
     _f, _b, _ln = KVCacheGenerator._f, KVCacheGenerator._b, KVCacheGenerator._ln
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def _drop_plan(self) -> None:
+        plan, self._plan = self._plan, None
+        if plan is not None:
+            L.load().ergm_decode_destroy(plan)
+
+    def __del__(self):
+        try:
+            self._drop_plan()
+        except Exception:
+            pass
+
+    def _bind_plan(self, Sc: int) -> None:
+        """(Re)create the executor plan when the captions outgrow it, then bind the state the prefill left."""
+        lib, lay = L.load(), self.m.layout
+        if self._plan is None or Sc > self._cap_max:
+            self._drop_plan()
+            self._cap_max = max(Sc, self.max_len)
+            dims = L.DecodeDims(vocab=lay.vocab, vocab_pad=lay.vocab_pad, n_embd=self.E, n_layer=self.L, n_head=self.H,
+                                n_inner=self.F, n_positions=self.cfg.n_positions, max_batch=self.max_batch,
+                                max_len=self.max_len, cap_max=self._cap_max, eps=self.cfg.layer_norm_epsilon)
+            prm = L.ModelParams()
+            prm.wte, prm.wte_b = self._f("__wte_pad").data_ptr(), self._b("__wte_pad").data_ptr()
+            prm.wpe = self._f("transformer.wpe.weight").data_ptr()
+            prm.ln_f_w = self._f("transformer.ln_f.weight").data_ptr()
+            prm.ln_f_b = self._f("transformer.ln_f.bias").data_ptr()
+            prm.layer_f32 = self.m.flat.data_ptr() + 4 * lay.layer_base[0]
+            prm.layer_b16 = self.m.flat_b16.data_ptr() + 2 * lay.layer_base[0]
+            prm.layer_stride = lay.layer_stride
+            for i, o in enumerate(lay.layer_off):
+                prm.layer_off[i] = o
+            need = lib.ergm_decode_workspace_size(C.byref(dims))
+            if need == 0:
+                raise ValueError("the decode executor does not support this model's dimensions")
+            self._plan_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            self._plan_params = prm
+            plan = C.c_void_p()
+            L.check(lib.ergm_decode_create(C.byref(dims), C.byref(prm), C.c_void_p(self._plan_ws.data_ptr()), need,
+                                           C.byref(plan)), "ergm_decode_create")
+            self._plan = plan
+            L.call("ergm_decode_set_engine", self._plan, self.ENGINES[self.engine])
+        ptrs = C.c_void_p * self.L
+        kv = ptrs(*[t.data_ptr() for t in self.kv])
+        xkv = ptrs(*[t.data_ptr() for t in self.xkv])
+        L.call("ergm_decode_bind", self._plan, self.B, self.n_max, kv, xkv, Sc, C.c_void_p(self.lens.data_ptr()),
+               C.c_void_p(self.cap_lens.data_ptr()), C.c_void_p(self.finished.data_ptr()),
+               C.c_void_p(self._logits.data_ptr()))
 
     def _gemm(self, x, name, n, N, K, **kw):
         return ops.gemm(x, self._b(name + ".weight"), n, N, K, L.MK, L.KN, bias=self._f(name + ".bias"), **kw)
@@ -275,6 +338,8 @@ class BatchedGenerator:
         self._ws = ops.attn_decode_workspace(B, H, max(self.max_len, Sc), dev)
         last = torch.tensor([b * S + lens[b] - 1 for b in range(B)], device=dev)
         self._logits = self._head(h.index_select(0, last))
+        if self.engine != "python":
+            self._bind_plan(Sc)
         return self._logits[:, :self.m.layout.vocab]
 
     @torch.no_grad()
@@ -289,6 +354,14 @@ class BatchedGenerator:
         tokens, token_types = tokens.reshape(-1), token_types.reshape(-1)
         if tokens.numel() != B or token_types.numel() != B:
             raise ValueError(f"step takes one token and one token type per sequence ({B})")
+        if self.engine != "python":   # the executor's step, into the logits buffer the prefill bound
+            if tokens.dtype != torch.int64 or token_types.dtype != torch.int64 or not (tokens.is_cuda and token_types.is_cuda):
+                raise ValueError("step takes int64 GPU tensors")
+            tokens, token_types = tokens.contiguous(), token_types.contiguous()
+            L.call("ergm_decode_step", self._plan, C.c_void_p(tokens.data_ptr()), C.c_void_p(token_types.data_ptr()),
+                   self._stream())
+            self.n_max += 1
+            return self._logits[:, :self.m.layout.vocab]
         lens, cap_lens = self.lens[:B], self.cap_lens[:B]
         h = ops.embed_rows(tokens, token_types, lens, self._f("__wte_pad"), self._f("transformer.wpe.weight"))
         for l in range(self.L):
@@ -326,6 +399,17 @@ class BatchedGenerator:
         tt = torch.full((B,), sp2_id, dtype=torch.int64, device=self.dev)
         fin = self.finished[:B]
         done = 0
+        if self.engine != "python":
+            while True:   # the executor samples and steps 8 tokens per call; the host looks in between, as below
+                n = min(8, max_new_tokens - done)
+                L.call("ergm_decode_run", self._plan, done, n, float(top_p), seed & (2 ** 64 - 1), eos_id, sp2_id,
+                       C.c_void_p(out.data_ptr()), self._stream())
+                self.n_max += n - (1 if done == 0 else 0)
+                done += n
+                if done == max_new_tokens or bool(fin.all()):
+                    break
+            rows = out[:done].t().cpu().tolist()
+            return [r[:r.index(eos_id) + 1] if eos_id in r else r for r in rows]
         for i in range(max_new_tokens):
             ops.topp_sample(self._logits, V, top_p, seed, i, eos_id, finished=fin, tokens=out[i])
             done = i + 1

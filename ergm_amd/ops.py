@@ -61,6 +61,34 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, a_layout: int
     return out
 
 
+def linear_rows(A: torch.Tensor, W: torch.Tensor, M: int, N: int, K: int, w_layout: int = L.KN,
+                out: Optional[torch.Tensor] = None, epilogue: int = L.EPI_NONE, bias: Optional[torch.Tensor] = None,
+                aux: Optional[torch.Tensor] = None, ln_gamma: Optional[torch.Tensor] = None,
+                ln_beta: Optional[torch.Tensor] = None, ln_eps: float = 1e-5) -> torch.Tensor:
+    """C[M,N] = epilogue(A'·W + bias) for a handful of rows (ergm_linear_rows): A bf16 [>= M, >= K], or f32 rows
+    that the kernel LayerNorms itself when ``ln_gamma`` / ``ln_beta`` are given; W bf16 [K, N] (KN) or [N, K] (NK).
+    The output dtype follows the epilogue: f32 for NONE and BIAS_RESID (``aux`` f32, may be ``out``), bf16 otherwise."""
+    _need_gpu(A, W)
+    ln = ln_gamma is not None or ln_beta is not None
+    if A.dtype != (torch.float32 if ln else torch.bfloat16) or W.dtype != torch.bfloat16:
+        raise ValueError("linear_rows: A is bf16 (f32 with the LayerNorm prologue), W bf16")
+    f32_out = epilogue in (L.EPI_NONE, L.EPI_BIAS_RESID)
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32 if f32_out else torch.bfloat16, device=A.device)
+    elif out.dtype != (torch.float32 if f32_out else torch.bfloat16):
+        raise ValueError("linear_rows: the output dtype does not match the epilogue")
+    for t in (bias, aux, ln_gamma, ln_beta):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise ValueError("linear_rows: bias, aux, ln_gamma and ln_beta are f32 GPU tensors")
+    d = L.LinearRowsDesc(M=M, N=N, K=K, lda=A.stride(0) if A.dim() == 2 else K,
+                         ldw=W.stride(0) if W.dim() == 2 else (N if w_layout == L.KN else K), ldc=out.stride(0),
+                         w_layout=w_layout, epilogue=epilogue, bias=_ptr(bias), aux=_ptr(aux),
+                         ld_aux=aux.stride(0) if aux is not None else 0, ln_gamma=_ptr(ln_gamma), ln_beta=_ptr(ln_beta),
+                         ln_eps=ln_eps)
+    L.check(L.load().ergm_linear_rows(C.byref(d), _ptr(A), _ptr(W), _ptr(out), _stream(A.device)), "ergm_linear_rows")
+    return out
+
+
 def gemm_f8(A8: torch.Tensor, a_scale: torch.Tensor, B8t: torch.Tensor, b_scale: torch.Tensor,
             out: Optional[torch.Tensor] = None, out_dtype=torch.float32, epilogue: int = L.EPI_NONE,
             bias: Optional[torch.Tensor] = None, aux: Optional[torch.Tensor] = None,

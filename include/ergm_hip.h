@@ -25,6 +25,10 @@
  *   ergm_adamw_step       torch.optim.AdamW.step (src/main.py:68,155)
  *   ergm_attn_decode, ergm_embed_rows, ergm_topp_sample
  *                         the per-token work of nucleus_sampling (src/main.py:253-282), for a batch
+ *   ergm_linear_rows      Conv1D / lm_head for the few rows of a decode step, with the nn.LayerNorm in front
+ *                         of it (src/model.py:298,318,332) computed in the same launch
+ *   ergm_decode_*         the token loop of nucleus_sampling (src/main.py:253-282) for a batch, after the
+ *                         prompt: one native launch sequence per step and per chunk of samples
  *   ergm_model_*          the whole GPT2LMHeadModel.forward (src/model.py:654-737) and its
  *                         backward (src/main.py:154) as one native launch sequence
  */
@@ -258,6 +262,34 @@ size_t ergm_attn_decode_workspace_size(int B, int H, int max_len);
 int ergm_attn_decode(const void* qkv, int ld_qkv, void* kcache, void* vcache, int64_t ld_seq, int ld_row,
                      const int* lens, int B, int H, int max_len, int append, int splits, void* out, int ldo,
                      void* workspace, size_t ws_bytes, void* stream);
+
+/* Linear layer for a handful of rows (a decode step: M = the batch, designed for M <= 32; any M >= 1 runs, the
+ * weights being streamed once per group of 32 rows), with an optional LayerNorm in front:
+ *   C[m][n] = epi( Σ_k A'[m][k]·W[k|n] + bias[n] ),   K % 64 == 0, N % 8 == 0
+ *   A' = A, bf16 [M][lda]                                     when ln_gamma == ln_beta == NULL
+ *   A' = bf16((x − μ_m)·rstd_m·γ + β), x = A as f32 [M][lda]   when both are given (biased variance and ln_eps as
+ *        ergm_layernorm_fwd; mean and variance in fp32 in two passes; the operand is rounded to bf16 once)
+ *   W bf16: ERGM_KN [K][ldw] (Conv1D) or ERGM_NK [N][ldw] (nn.Linear, the tied LM head)
+ *   epi: NONE (f32 C) | BIAS (bf16 C) | BIAS_GELU (bf16 C = gelu_new, no derivative output) |
+ *        BIAS_RESID (f32 C = aux[m][n] + v + bias[n], aux f32 [M][ld_aux], aux may be C); either weight layout.
+ * One launch, no workspace (there is no _workspace_size query), no atomics: K is split over the waves of one
+ * workgroup per 16-column strip and the partials are summed in a fixed order, so the same inputs give the same bits
+ * in every run.  A row's result depends on no other row: row r of a call on M rows equals, bitwise, a call on that
+ * row alone.  Rows at or past M are neither read nor written.  lda: a multiple of 8 elements (4 with the LayerNorm),
+ * ldw of 8; A, W, ln_gamma, ln_beta 16-byte aligned.  Unsupported arguments: ERGM_EINVAL before any launch.       */
+typedef struct {
+    int M, N, K;
+    int lda, ldw, ldc;
+    int w_layout;            /* ergm_b_layout */
+    int epilogue;            /* ergm_epilogue: NONE, BIAS, BIAS_GELU or BIAS_RESID */
+    const float* bias;       /* [N] f32; NULL only with NONE */
+    const float* aux;        /* BIAS_RESID: f32 residual [M][ld_aux] */
+    int ld_aux;
+    const float* ln_gamma;   /* [K] f32, or NULL: no LayerNorm */
+    const float* ln_beta;    /* [K] f32 */
+    float ln_eps;
+} ergm_linear_rows_desc;
+int ergm_linear_rows(const ergm_linear_rows_desc* desc, const void* A, const void* W, void* C, void* stream);
 
 /* LayerNorm over rows of E (biased variance, eps): y(bf16) = (x-μ)·rstd·γ + β; x f32.        */
 int ergm_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, float* mean,
@@ -579,6 +611,62 @@ int ergm_model_probe_count(const ergm_model_plan* plan);
 /* Copies the head stage's data gradient dy [batch*seq][n_embd] f32 (the LM-head dX plus the emotion head's rows
  * seq-1) to dst on `stream`: valid between ergm_model_backward_head and the next training forward (ABI 12). */
 int ergm_model_copy_head_dy(ergm_model_plan* plan, float* dst, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Decode executor: one generation step of B ragged sequences (ergm_amd/generate.py BatchedGenerator.step) and
+ * the sampling loop around it as native launch sequences.  Like ergm_model_plan the plan records pointers and
+ * dimensions only; creating and destroying one touches no GPU.  Everything runs on the caller's one stream: no
+ * events, no second stream, no graph capture, nothing synchronises and no device memory is read on the host.
+ * The prompt is encoded by the caller (the training kernels; generate.py's prefill), which then binds its caches.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct ergm_decode_plan ergm_decode_plan;
+typedef struct {
+    int vocab, vocab_pad, n_embd, n_layer, n_head, n_inner, n_positions;
+    int max_batch;            /* sequences at most */
+    int max_len;              /* rows of every sequence's self-attention cache, <= n_positions */
+    int cap_max;              /* caption rows at most (Sc of ergm_decode_bind) */
+    float eps;
+} ergm_decode_dims;
+/* Bytes of device workspace of a plan (the step's activations and the kernels' scratch); host only.  0 for
+ * dimensions ergm_decode_create rejects: n_head·64 == n_embd <= 1024, n_inner % 64 == 0, vocab_pad % 64 == 0,
+ * 1 <= max_len <= n_positions, max_batch, cap_max, n_layer >= 1.                                              */
+size_t ergm_decode_workspace_size(const ergm_decode_dims* dims);
+/* params: only the forward pointers are read (wte, wte_b, wpe, ln_f_w, ln_f_b, layer_f32, layer_b16, layer_stride,
+ * layer_off).  workspace: 256-byte aligned, ws_bytes >= ergm_decode_workspace_size(dims).                       */
+int ergm_decode_create(const ergm_decode_dims* dims, const ergm_model_params* params, void* workspace,
+                       size_t ws_bytes, ergm_decode_plan** out_plan);
+int ergm_decode_destroy(ergm_decode_plan* plan);
+/* The state of B <= max_batch sequences after the prefill (device pointers the caller owns and keeps valid):
+ *   kv[l]    layer l's self-attention cache, bf16 [max_batch][max_len][2·n_embd], K | V of a position in one row
+ *   xkv[l]   layer l's caption K | V, bf16 [B][Sc][2·n_embd], 1 <= Sc <= cap_max
+ *   lens     int [B] cache lengths (in/out: a step adds 1 for every sequence not yet finished); n_max = the host's
+ *            bound on max(lens), which the plan advances by one per step
+ *   cap_lens int [B] caption lengths; finished uint8 [B] (ergm_topp_sample's flags); logits f32 [B][vocab_pad], written
+ *            by every step.  The pointer arrays kv / xkv (n_layer host entries each) are copied.                */
+int ergm_decode_bind(ergm_decode_plan* plan, int B, int n_max, void* const* kv, void* const* xkv, int Sc, int* lens,
+                     const int* cap_lens, uint8_t* finished, float* logits);
+/* engine 0 (default): the kernels generate.py's Python step calls, launch for launch with the same arguments
+ * (ergm_layernorm_fwd, ergm_gemm with split_k = 0, ergm_attn_decode with splits = 0): every buffer is bitwise what
+ * that path writes.  engine 1: every LayerNorm + GEMM pair and every plain GEMM of the blocks is one
+ * ergm_linear_rows launch (8 launches per block instead of 11); the head stays ergm_layernorm_fwd + ergm_gemm, which
+ * measured faster at vocabulary width.                                                            */
+int ergm_decode_set_engine(ergm_decode_plan* plan, int engine);
+/* One step: ergm_embed_rows of `tokens` / `token_types` (device int64 [B]; token_types may be NULL) at lens, the
+ * n_layer blocks (self-attention appends the new K | V row to kv), ln_f and the tied head into logits, then
+ * lens[b] += !finished[b].  ERGM_EINVAL, before any launch, without a bind or with the cache full (n_max >= max_len). */
+int ergm_decode_step(ergm_decode_plan* plan, const int64_t* tokens, const int64_t* token_types, void* stream);
+/* Samples i = first .. first+n-1 of nucleus sampling (generate.py's loop): for i > 0 a step on tokens_out[i-1] typed
+ * sp2_id, then ergm_topp_sample(logits, vocab, top_p, seed, step = i, finished, eos_id) into tokens_out[i]
+ * (device int64 [>= first+n][B]).  A row that has just drawn eos is stepped once more without advancing its length.
+ * Enqueues and returns.  ERGM_EINVAL before any launch when n < 1, first < 0 or the steps would overrun the cache.
+ * `first` is the caller's count of samples already drawn since the bind: the plan does not check it.  After any other
+ * failure (a launch error part-way) bind again before going on.                                                     */
+int ergm_decode_run(ergm_decode_plan* plan, int first, int n, float top_p, uint64_t seed, int64_t eos_id,
+                    int64_t sp2_id, int64_t* tokens_out, void* stream);
+/* Kernel launches one ergm_decode_step enqueues with `engine`, for the bound batch (max_batch before a bind) and the
+ * GEMM / attention plans as they stand now: counted by walking the step's own launch sequence dry.  Host only;
+ * negative ergm_status on a bad argument.                                                                          */
+int ergm_decode_launches(const ergm_decode_plan* plan, int engine);
 
 /* Library information and errors. */
 int ergm_version(void);

@@ -4,7 +4,10 @@ Workload: GPT-2-small (random weights, so the nucleus is most of the vocabulary)
 tokens, top_p 0.95, an eos id no token has (every sequence runs to the bound).  tokens/s = B·64 over the time of the
 whole call (prefill + sampling + decode), HIP events around it, 1 warm-up and the median of 5 repeats, for
   kv       KVCacheGenerator.nucleus_sampling, one sequence (the baseline)
-  b1/8/32  BatchedGenerator.generate at B = 1, 8, 32
+  b1/8/32  BatchedGenerator.generate at B = 1, 8, 32 (engine "python": every launch enqueued from Python)
+  n1/8/32  the same through the native decode executor on the same kernels (engine "native")
+  f1/8/32  the executor on ergm_linear_rows (engine "fused"); with ERGM_DECODE_HEAD=lr or ln in the environment the
+           LM head runs on that kernel too, behind ergm_layernorm_fwd (lr) or with the LayerNorm in its prologue (ln)
 and ``attn``: ergm_attn_decode (append = 0, H = 12) at cache lengths 128 and 1,024 for B = 1 and 32, bytes/s = the
 K/V bytes of the attended rows over the mean time of 200 back-to-back launches (median of 5 such windows), the
 caches rotated through enough buffers to exceed the 256 MiB Infinity Cache where memory allows; set against the
@@ -15,7 +18,10 @@ and divide the same byte count by the mean duration of attn_decode_kernel (plus 
 automatic split is above 1).
 
 Without --case the tool runs every case in turn, each in a fresh child process under its own timeout, one at a
-time, and stops at the first that fails.  Usage (GPU box): python tools/gen_bench.py [--case kv|b1|b8|b32|attn]"""
+time, and stops at the first that fails.  --cases a,b,c runs those cases in that
+order (e.g. b32,n32,f32,b32,n32,f32 to alternate engines on one box).  For the kernel-time split of one engine:
+  rocprofv3 --kernel-trace --stats -d OUT -- python tools/gen_bench.py --case f32
+Usage (GPU box): python tools/gen_bench.py [--case kv|b1|b8|b32|n*|f*|attn] [--cases LIST]"""
 import json
 import os
 import statistics
@@ -24,7 +30,8 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-CASES = {"kv": 240, "b1": 240, "b8": 240, "b32": 240, "attn": 240}  # seconds each child may take
+ENGINES = {"b": "python", "n": "native", "f": "fused"}
+CASES = {"kv": 240, **{e + b: 240 for e in ENGINES for b in ("1", "8", "32")}, "attn": 240}  # seconds a child may take
 PROMPT = CAPS = NEW = 64
 TOP_P, NO_EOS, SP2 = 0.95, -1, 50259
 REPEATS = 5
@@ -59,7 +66,7 @@ def _generation(case):
                                        generator=torch.Generator(device=dev).manual_seed(7))
             assert len(out) == NEW
     else:
-        gen = BatchedGenerator(model, max_batch=B, max_len=PROMPT + NEW)
+        gen = BatchedGenerator(model, max_batch=B, max_len=PROMPT + NEW, engine=ENGINES[case[0]])
 
         def run():
             out = gen.generate(prompts, top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2, seed=7, max_new_tokens=NEW)
@@ -67,7 +74,7 @@ def _generation(case):
     run()  # warm-up: code objects, GEMM plans, allocator
     ms = [_event_ms(run) for _ in range(REPEATS)]
     med = statistics.median(ms)
-    print(json.dumps({"case": case, "B": B, "new_tokens": NEW, "ms_median": round(med, 2),
+    print(json.dumps({"case": case, "engine": "single" if case == "kv" else ENGINES[case[0]], "B": B, "new_tokens": NEW, "ms_median": round(med, 2),
                       "ms_all": [round(x, 2) for x in ms], "tokens_per_s": round(B * NEW / med * 1e3, 1)}), flush=True)
 
 
@@ -107,7 +114,11 @@ def main():
             raise SystemExit(f"unknown case {case}")
         _attention() if case == "attn" else _generation(case)
         return
-    for case, limit in CASES.items():
+    order = sys.argv[sys.argv.index("--cases") + 1].split(",") if "--cases" in sys.argv else list(CASES)
+    for case in order:
+        if case not in CASES:
+            raise SystemExit(f"unknown case {case}")
+        limit = CASES[case]
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", case], timeout=limit)
         except subprocess.TimeoutExpired:
