@@ -103,11 +103,15 @@ _SIGS = {
     "ergm_quant_rows_mx": (i32, [vp, i32, i32, i32, i32, vp, i32, vp, i32, vp]),
     "ergm_quant_weight_mx": (i32, [vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp]),
     "ergm_attn_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "ergm_attn_fwd_ragged": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp] + [i32] * 11 + [vp]),
     "ergm_attn_tune": (i32, [i32]),
     "ergm_attn_decode_workspace_size": (sz, [i32, i32, i32]),
     "ergm_attn_decode": (i32, [vp, i32, vp, vp, i64, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, sz, vp]),
     "ergm_embed_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ergm_topp_sample": (i32, [vp, i32, i32, i32, f32, C.c_uint64, C.c_uint32, vp, i64, vp, vp, vp, vp]),
+    "ergm_topp_sample_rows": (i32, [vp, i32, i32, i32, f32, C.c_uint64, vp, vp, vp, i64, vp, vp, vp, vp]),
+    "ergm_rows_to_slots": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp, i64, i64, i32, i32, i32, vp]),
+    "ergm_embed_packed": (i32, [vp] * 12 + [i32] * 5 + [vp, vp, i32, i32, i32, i32, vp]),
     "ergm_attn_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp] + [i32] * 13 + [vp, vp, vp]),
     "ergm_linear_rows": (i32, [C.POINTER(LinearRowsDesc), vp, vp, vp, vp]),
     "ergm_decode_workspace_size": (sz, [C.POINTER(DecodeDims)]),
@@ -118,6 +122,13 @@ _SIGS = {
     "ergm_decode_step": (i32, [vp, vp, vp, vp]),
     "ergm_decode_run": (i32, [vp, i32, i32, f32, C.c_uint64, i64, i64, vp, vp]),
     "ergm_decode_launches": (i32, [vp, i32]),
+    "ergm_decode_bind_slots": (i32, [vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp, vp, vp, vp]),
+    "ergm_decode_admit_workspace_size": (sz, [C.POINTER(DecodeDims), i32, i32]),
+    "ergm_decode_admit": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, vp, vp, vp, vp,
+                                vp, vp, vp, sz, vp]),
+    "ergm_decode_admit_launches": (i32, [vp, i32, i32, i32]),
+    "ergm_decode_step_slots": (i32, [vp, vp, vp, vp]),
+    "ergm_decode_run_slots": (i32, [vp, i32, f32, C.c_uint64, i64, i64, vp, vp]),
     "ergm_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "ergm_layernorm_bwd_workspace_size": (sz, [i32, i32]),
     "ergm_layernorm_bwd": (i32, [vp] * 10 + [sz, i32, i32, vp, vp]),
@@ -168,6 +179,7 @@ _SIGS = {
     "ergm_model_set_logits_grad": (i32, [vp, vp]),
     "ergm_model_stage_wait": (i32, [vp, i32, vp]),
 }
+ADMIT_META_ROWS = 10  # ERGM_ADMIT_META_ROWS
 EXPORTED = sorted(_SIGS)
 
 _lib = None

@@ -244,6 +244,8 @@ __device__ __forceinline__ float stored_keep(const uint64_t* mrow, int key, floa
 }
 
 // Normalised output row (bf16) and the log-sum-exp (natural log, scaled scores) of this lane's query.
+// LSE = false (the ragged inference forward without an LSE buffer): the row only.
+template <bool LSE = true>
 __device__ __forceinline__ void fwd_store(const AttnArgs& a, int b, int h, int q, const f32x4 (&o)[4], float m,
                                           float l) {
     const int g = (threadIdx.x & 63) >> 4;
@@ -284,7 +286,8 @@ __device__ __forceinline__ void fwd_store(const AttnArgs& a, int b, int h, int q
         for (int r = 0; r < 4; ++r) w[r] = f2bf(o[d][r] * inv);
         *reinterpret_cast<bf16x4*>(Ob + d * 16 + 4 * g) = w;
     }
-    if (g == 0) a.lse[((size_t)b * a.H + h) * a.Sq + q] = m * a.scale + logf(l);
+    if constexpr (LSE)
+        if (g == 0) a.lse[((size_t)b * a.H + h) * a.Sq + q] = m * a.scale + logf(l);
 }
 
 // dK/dV contribution of one 64-query tile (Q, dO, LSE, δ staged) for this lane's key: P recomputed,
@@ -504,6 +507,75 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_fwd_kernel(AttnArgs a)
                                arow, mrow ? mrow + kt : nullptr);
     }
     fwd_store(a, b, h, q, o, m, l);
+}
+
+// Inference forward over a packed batch of sequences of different lengths (ergm_attn_fwd_ragged): sequence b owns
+// the query rows q_start[b] .. q_start[b] + q_len[b] - 1 of the packed Q / O buffers and the key rows k_start[b] ..
+// k_start[b] + k_len[b] - 1 of the packed K / V buffers.  The grid is rectangular, (query tiles of the longest
+// sequence, H, sequences); a workgroup whose tile lies past its sequence's last row exits before it touches memory
+// or a barrier.  Query tiles are counted from the sequence's own first row (causal: the last tile, the longest key
+// loop, first), so the workgroup of (sequence, tile, head) runs attn_fwd_kernel's loop on the tiles attn_fwd_kernel
+// sees for that sequence alone (B = 1, Sq = q_len[b], Sk = k_len[b]): the output rows are bitwise the same.
+// Everything read from the metadata arrays is clamped to the packed extents before an address is formed.
+struct RaggedMeta {
+    const int *q_start, *q_len, *k_start, *k_len;
+    int total_q, total_k;  // packed rows of Q / O and of K / V
+    int max_q, max_k;      // host bounds on q_len / k_len (max_q sizes the grid)
+};
+
+template <bool CAUSAL, int NS, bool LSE>
+__global__ __launch_bounds__(256, 4) void attn_fwd_ragged_kernel(AttnArgs a, RaggedMeta r) {
+    __shared__ __attribute__((aligned(16))) char ring[NS * 2 * AT_TILE_BYTES];  // [stage][K|V]
+    const int b = blockIdx.z, h = blockIdx.y;
+    const int n = max(0, min(r.q_len[b], min(r.max_q, r.total_q)));
+    const int Sk = max(0, min(r.k_len[b], min(r.max_k, r.total_k)));
+    const int ntile = (n + AT_T - 1) / AT_T;
+    if ((int)blockIdx.x >= ntile) return;  // uniform over the workgroup
+    const int qs = max(0, min(r.q_start[b], r.total_q - n));
+    const int ks = max(0, min(r.k_start[b], r.total_k - Sk));
+    a.Sq = n;
+    a.Sk = Sk;
+    a.out += (size_t)qs * a.ldo;
+    if (LSE) a.lse += (size_t)qs * a.H;  // [H][q_len[b]] of sequence b starts at H·q_start[b]
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int i16 = lane & 15, g = lane >> 4;
+    const int qblk = (CAUSAL ? ntile - 1 - (int)blockIdx.x : (int)blockIdx.x) * AT_T;
+    const int q = qblk + wave * 16 + i16;  // this lane's query, counted from the sequence's first row
+    const float c = a.scale * AT_LOG2E;
+    const __bf16* Qb = a.q + (size_t)qs * a.ldq + h * AT_D;
+    const __bf16* Kb = a.k + (size_t)ks * a.ldk + h * AT_D;
+    const __bf16* Vb = a.v + (size_t)ks * a.ldv + h * AT_D;
+
+    bf16x8 qf[2];
+    qf[0] = load_frag_global(Qb, a.ldq, q, a.Sq, 8 * g);
+    qf[1] = load_frag_global(Qb, a.ldq, q, a.Sq, 32 + 8 * g);
+    vm_ready(qf[0]);
+    vm_ready(qf[1]);
+
+    f32x4 o[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+
+    int nkt = (a.Sk + AT_T - 1) / AT_T;
+    if (CAUSAL) {
+        int qlast = min(a.Sq, qblk + AT_T) - 1;
+        nkt = min(nkt, qlast / AT_T + 1);
+    }
+    auto issue = [&](int kt) {
+        char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
+        AttnTile::issue(st, Kb, a.ldk, kt * AT_T, a.Sk, 0, wave);
+        AttnTile::issue(st + AT_TILE_BYTES, Vb, a.ldv, kt * AT_T, a.Sk, 0, wave);
+    };
+    for (int s = 0; s < NS - 1 && s < nkt; ++s) issue(s);
+    for (int kt = 0; kt < nkt; ++kt) {
+        ring_sync<4, NS>(min(NS - 2, nkt - 1 - kt));
+        if (kt + NS - 1 < nkt) issue(kt + NS - 1);
+        const char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
+        fwd_tile<CAUSAL, false>(st, st + AT_TILE_BYTES, kt * AT_T, q, qblk + wave * 16, a.Sk, c, qf, o, m, l, a.drop, 0,
+                                nullptr);
+    }
+    fwd_store<LSE>(a, 0, h, q, o, m, l);
 }
 
 // Cross-attention forward with the query projection inside (non-causal): the workgroup of (query block, h, b)
@@ -1182,6 +1254,40 @@ int ergm::attn_fwd_mx(const void* q, const void* k, const void* v, void* o, floa
     if (causal) drop ? tiled_fwd<true, true>(grid, s, a) : tiled_fwd<true, false>(grid, s, a);
     else drop ? tiled_fwd<false, true>(grid, s, a) : tiled_fwd<false, false>(grid, s, a);
     return check_launch("attn_fwd");
+}
+
+extern "C" int ergm_attn_fwd_ragged(const void* q, const void* k, const void* v, void* o, float* lse, const int* q_start,
+                                    const int* q_len, const int* k_start, const int* k_len, int n_seq, int H,
+                                    int total_q, int total_k, int max_q, int max_k, int ldq, int ldk, int ldv, int ldo,
+                                    int causal, void* stream) {
+    ERGM_CHECK_ARG(q && k && v && o && q_start && q_len && k_start && k_len, "attn_fwd_ragged: null argument");
+    ERGM_CHECK_ARG(n_seq > 0 && n_seq <= 65535 && H > 0 && H <= 65535, "attn_fwd_ragged: bad shape n_seq %d H %d", n_seq, H);
+    ERGM_CHECK_ARG(total_q > 0 && total_k > 0 && max_q > 0 && max_q <= total_q && max_k > 0 && max_k <= total_k,
+                   "attn_fwd_ragged: bad extents total_q %d total_k %d max_q %d max_k %d", total_q, total_k, max_q, max_k);
+    ERGM_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0,
+                   "attn_fwd_ragged: leading dims must be multiples of 8 (output: 4)");
+    ERGM_CHECK_ARG(ldq >= H * AT_D && ldk >= H * AT_D && ldv >= H * AT_D && ldo >= H * AT_D,
+                   "attn_fwd_ragged: leading dim < H*64");
+    ERGM_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v), "attn_fwd_ragged: pointers must be 16-byte aligned");
+    AttnArgs a{};
+    a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v;
+    a.out = (__bf16*)o; a.lse = lse;
+    a.B = 1; a.H = H;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.scale = 0.125f;
+    const RaggedMeta r{q_start, q_len, k_start, k_len, total_q, total_k, max_q, max_k};
+    const dim3 grid(cdiv(max_q, AT_T), H, n_seq);
+    hipStream_t s = as_stream(stream);
+    // two ring stages, the tiled forward's default (the stage count does not enter the arithmetic; ergm_attn_tune's
+    // measurement switch is not consulted here)
+    if (causal) {
+        if (lse) ERGM_LAUNCH((attn_fwd_ragged_kernel<true, 2, true>), grid, dim3(256), 0, s, a, r);
+        else ERGM_LAUNCH((attn_fwd_ragged_kernel<true, 2, false>), grid, dim3(256), 0, s, a, r);
+    } else {
+        if (lse) ERGM_LAUNCH((attn_fwd_ragged_kernel<false, 2, true>), grid, dim3(256), 0, s, a, r);
+        else ERGM_LAUNCH((attn_fwd_ragged_kernel<false, 2, false>), grid, dim3(256), 0, s, a, r);
+    }
+    return check_launch("attn_fwd_ragged");
 }
 
 extern "C" int ergm_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,

@@ -235,9 +235,10 @@ __device__ __forceinline__ float tp_use(float e) {
 template <int NPT>
 __global__ __launch_bounds__(TP_THREADS) void topp_sample_kernel(const float* __restrict__ logits, int ldl, int V,
                                                                  float top_p, uint32_t seed_lo, uint32_t seed_hi,
-                                                                 uint32_t step, uint8_t* finished, int64_t eos_id,
-                                                                 int64_t* __restrict__ tokens, int* __restrict__ kept,
-                                                                 float* __restrict__ kept_mass) {
+                                                                 uint32_t step, const uint32_t* __restrict__ row_ids,
+                                                                 const uint32_t* __restrict__ row_steps, uint8_t* finished,
+                                                                 int64_t eos_id, int64_t* __restrict__ tokens,
+                                                                 int* __restrict__ kept, float* __restrict__ kept_mass) {
     __shared__ TpShared sm;
     const int b = blockIdx.x, t = threadIdx.x;
     if (finished && finished[b]) {  // uniform over the workgroup
@@ -344,7 +345,9 @@ __global__ __launch_bounds__(TP_THREADS) void topp_sample_kernel(const float* __
     unsigned long long K;
     unsigned long long run = tp_scan(mine, sm.scan, K);
     // the draw: first kept token, in token order, whose running sum reaches u·K
-    const uint4 r = philox4x32_10(make_uint4((uint32_t)b, 0u, 0xE5A3u, step), seed_lo, seed_hi);
+    // the counter's row and step: the workgroup's own row and the call's step, or (ergm_topp_sample_rows) per row
+    const uint32_t crow = row_ids ? row_ids[b] : (uint32_t)b, cstep = row_steps ? row_steps[b] : step;
+    const uint4 r = philox4x32_10(make_uint4(crow, 0u, 0xE5A3u, cstep), seed_lo, seed_hi);
     const double u = ((double)r.x + 0.5) * (1.0 / 4294967296.0);
     unsigned long long target = (unsigned long long)ceil(u * (double)K);
     target = max(1ull, min(target, K));
@@ -381,6 +384,71 @@ __global__ void lens_advance_kernel(int* __restrict__ lens, const uint8_t* __res
 __global__ void fill_i64_kernel(int64_t* __restrict__ p, int64_t v, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
+}
+
+// ---- continuous batching: packed rows into cache slots, and the slot state (decode_exec.cpp) -------------
+// Row t of sequence b (packed row start[b] + t of src) goes to dst + slot[b]·ld_slot + t·ld_row; strides and
+// row_bytes in bytes, 16-byte copies, one wave per row.  Everything read from the device arrays is checked before an
+// address is formed: the length is clamped to [0, min(max_rows, slot_rows)], the start to the packed extent, and a
+// sequence whose slot lies outside [0, n_slots) writes nothing.
+__global__ __launch_bounds__(256) void rows_to_slots_kernel(const char* __restrict__ src, int64_t ld_src,
+                                                            const int* __restrict__ start, const int* __restrict__ len,
+                                                            const int* __restrict__ slot, int total_rows, int max_rows,
+                                                            char* __restrict__ dst, int64_t ld_slot, int64_t ld_row,
+                                                            int row_bytes, int n_slots, int slot_rows) {
+    const int b = blockIdx.y, t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int n = max(0, min(len[b], min(min(max_rows, slot_rows), total_rows)));
+    const int sl = slot[b];
+    if (t >= n || sl < 0 || sl >= n_slots) return;
+    const int r0 = max(0, min(start[b], total_rows - n));
+    const char* s = src + (int64_t)(r0 + t) * ld_src;
+    char* d = dst + (int64_t)sl * ld_slot + (int64_t)t * ld_row;
+    for (int c = lane * 16; c < row_bytes; c += 64 * 16)
+        *reinterpret_cast<uint4*>(d + c) = *reinterpret_cast<const uint4*>(s + c);
+}
+
+// The state of the slots an admission filled: one thread per admitted sequence.
+__global__ void slots_admit_kernel(const int* __restrict__ slot, const int* __restrict__ n_tok, const int* __restrict__ n_cap,
+                                   const int* __restrict__ max_new, const uint32_t* __restrict__ req, int n_seq, int n_slots,
+                                   int max_len, int cap_max, int* __restrict__ lens, int* __restrict__ cap_lens,
+                                   int* __restrict__ stop_lens, uint32_t* __restrict__ row_ids,
+                                   uint32_t* __restrict__ row_steps, uint8_t* __restrict__ finished) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_seq) return;
+    const int sl = slot[b];
+    if (sl < 0 || sl >= n_slots) return;
+    const int n = max(0, min(n_tok[b], max_len));
+    lens[sl] = n;
+    cap_lens[sl] = max(0, min(n_cap[b], cap_max));
+    stop_lens[sl] = max(n, min(n + max(max_new[b], 0), max_len));
+    row_ids[sl] = req[b];
+    row_steps[sl] = 0u;
+    finished[sl] = 0;
+}
+
+// The length update of a step over every slot: a live row advances by the token just appended and its draw counter
+// with it, and finishes when it reaches the bound recorded at its admission, so no row passes its bound whatever the
+// host does between two looks.
+__global__ void slots_advance_kernel(int* __restrict__ lens, uint32_t* __restrict__ row_steps, uint8_t* __restrict__ finished,
+                                     const int* __restrict__ stop_lens, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B || finished[b]) return;
+    const int n = lens[b] + 1;
+    lens[b] = n;
+    row_steps[b] += 1u;
+    if (n >= stop_lens[b]) finished[b] = 1;
+}
+
+int decode_slots_admit(const int* slot, const int* n_tok, const int* n_cap, const int* max_new, const uint32_t* req, int n_seq,
+                       int n_slots, int max_len, int cap_max, int* lens, int* cap_lens, int* stop_lens, uint32_t* row_ids,
+                       uint32_t* row_steps, uint8_t* finished, hipStream_t s) {
+    ERGM_LAUNCH(slots_admit_kernel, dim3(cdiv(n_seq, 256)), dim3(256), 0, s, slot, n_tok, n_cap, max_new, req, n_seq, n_slots,
+                max_len, cap_max, lens, cap_lens, stop_lens, row_ids, row_steps, finished);
+    return check_launch("decode_slots_admit");
+}
+int decode_slots_advance(int* lens, uint32_t* row_steps, uint8_t* finished, const int* stop_lens, int B, hipStream_t s) {
+    ERGM_LAUNCH(slots_advance_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, lens, row_steps, finished, stop_lens, B);
+    return check_launch("decode_slots_advance");
 }
 
 int decode_lens_advance(int* lens, const uint8_t* finished, int B, hipStream_t s) {
@@ -444,23 +512,59 @@ extern "C" int ergm_embed_rows(const int64_t* ids, const int64_t* tt, const int*
     return check_launch("embed_rows");
 }
 
-extern "C" int ergm_topp_sample(const float* logits, int ldl, int B, int V, float top_p, uint64_t seed, uint32_t step,
-                                void* finished, int64_t eos_id, int64_t* tokens, int* kept, float* kept_mass,
-                                void* stream) {
-    ERGM_CHECK_ARG(logits && tokens, "topp_sample: null argument");
-    ERGM_CHECK_ARG(B > 0 && V > 0 && ldl >= V, "topp_sample: bad shape B %d V %d ldl %d", B, V, ldl);
-    ERGM_CHECK_ARG(top_p == top_p, "topp_sample: top_p is NaN");
-    if (V > 52 * TP_THREADS) return fail(ERGM_EUNSUPPORTED, "topp_sample: V %d > %d", V, 52 * TP_THREADS);
+namespace {
+int topp_launch(const char* what, const float* logits, int ldl, int B, int V, float top_p, uint64_t seed, uint32_t step,
+                const uint32_t* row_ids, const uint32_t* row_steps, void* finished, int64_t eos_id, int64_t* tokens,
+                int* kept, float* kept_mass, void* stream) {
+    ERGM_CHECK_ARG(logits && tokens, "%s: null argument", what);
+    ERGM_CHECK_ARG(B > 0 && V > 0 && ldl >= V, "%s: bad shape B %d V %d ldl %d", what, B, V, ldl);
+    ERGM_CHECK_ARG(top_p == top_p, "%s: top_p is NaN", what);
+    if (V > 52 * TP_THREADS) return fail(ERGM_EUNSUPPORTED, "%s: V %d > %d", what, V, 52 * TP_THREADS);
     hipStream_t s = as_stream(stream);
     auto* fin = reinterpret_cast<uint8_t*>(finished);
     const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
     const int per = cdiv(V, TP_THREADS);
 #define ERGM_TOPP(NPT)                                                                                              \
-    ERGM_LAUNCH(topp_sample_kernel<NPT>, dim3(B), dim3(TP_THREADS), 0, s, logits, ldl, V, top_p, lo, hi, step, fin, \
-                eos_id, tokens, kept, kept_mass)
+    ERGM_LAUNCH(topp_sample_kernel<NPT>, dim3(B), dim3(TP_THREADS), 0, s, logits, ldl, V, top_p, lo, hi, step, row_ids, \
+                row_steps, fin, eos_id, tokens, kept, kept_mass)
     if (per <= 4) ERGM_TOPP(4);
     else if (per <= 16) ERGM_TOPP(16);
     else ERGM_TOPP(52);
 #undef ERGM_TOPP
-    return check_launch("topp_sample");
+    return check_launch(what);
+}
+}  // namespace
+
+extern "C" int ergm_topp_sample(const float* logits, int ldl, int B, int V, float top_p, uint64_t seed, uint32_t step,
+                                void* finished, int64_t eos_id, int64_t* tokens, int* kept, float* kept_mass,
+                                void* stream) {
+    return topp_launch("topp_sample", logits, ldl, B, V, top_p, seed, step, nullptr, nullptr, finished, eos_id, tokens, kept,
+                       kept_mass, stream);
+}
+
+extern "C" int ergm_topp_sample_rows(const float* logits, int ldl, int B, int V, float top_p, uint64_t seed,
+                                     const uint32_t* row_ids, const uint32_t* row_steps, void* finished, int64_t eos_id,
+                                     int64_t* tokens, int* kept, float* kept_mass, void* stream) {
+    ERGM_CHECK_ARG(row_ids && row_steps, "topp_sample_rows: null row_ids or row_steps");
+    return topp_launch("topp_sample_rows", logits, ldl, B, V, top_p, seed, 0u, row_ids, row_steps, finished, eos_id, tokens,
+                       kept, kept_mass, stream);
+}
+
+extern "C" int ergm_rows_to_slots(const void* src, int64_t ld_src, const int* start, const int* len, const int* slot,
+                                  int n_seq, int total_rows, int max_rows, void* dst, int64_t ld_slot, int64_t ld_row,
+                                  int row_bytes, int n_slots, int slot_rows, void* stream) {
+    ERGM_CHECK_ARG(src && start && len && slot && dst, "rows_to_slots: null argument");
+    ERGM_CHECK_ARG(n_seq > 0 && n_seq <= 65535 && total_rows > 0 && max_rows > 0 && max_rows <= total_rows && n_slots > 0 &&
+                       slot_rows > 0,
+                   "rows_to_slots: bad shape n_seq %d total_rows %d max_rows %d n_slots %d slot_rows %d", n_seq, total_rows,
+                   max_rows, n_slots, slot_rows);
+    ERGM_CHECK_ARG(row_bytes > 0 && row_bytes % 16 == 0 && ld_src % 16 == 0 && ld_slot % 16 == 0 && ld_row % 16 == 0,
+                   "rows_to_slots: row_bytes and the strides (bytes) must be multiples of 16");
+    ERGM_CHECK_ARG(ld_src >= row_bytes && ld_row >= row_bytes && ld_slot >= (int64_t)(slot_rows - 1) * ld_row + row_bytes,
+                   "rows_to_slots: stride shorter than the rows it spans");
+    ERGM_CHECK_ARG(aligned16(src) && aligned16(dst), "rows_to_slots: 16-byte alignment");
+    ERGM_LAUNCH(rows_to_slots_kernel, dim3(cdiv(std::min(max_rows, slot_rows), 4), n_seq), dim3(256), 0, as_stream(stream),
+                reinterpret_cast<const char*>(src), ld_src, start, len, slot, total_rows, max_rows,
+                reinterpret_cast<char*>(dst), ld_slot, ld_row, row_bytes, n_slots, slot_rows);
+    return check_launch("rows_to_slots");
 }

@@ -5,6 +5,10 @@
 // returns before calling anything, so ergm_decode_launches reports what ergm_decode_step enqueues.  Engine 0 calls
 // the C-ABI entry points the Python path calls, with its arguments; engine 1 puts ergm_linear_rows in the
 // place of each LayerNorm + GEMM pair and each plain GEMM of the blocks.
+//
+// Slot mode (ergm_decode_bind_slots) serves ContinuousGenerator: the same step over all max_batch cache slots with the
+// slot length update at its end, and the admission of new sequences into free slots (walk_admit: the prefill over
+// packed ragged rows, written once like the step so that ergm_decode_admit_launches counts what runs).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +23,10 @@ namespace ergm {
 int decode_lens_advance(int* lens, const uint8_t* finished, int B, hipStream_t s);
 int decode_fill_i64(int64_t* p, int64_t v, int n, hipStream_t s);
 int attn_decode_launches(int B, int H, int max_len);
+int decode_slots_admit(const int* slot, const int* n_tok, const int* n_cap, const int* max_new, const uint32_t* req, int n_seq,
+                       int n_slots, int max_len, int cap_max, int* lens, int* cap_lens, int* stop_lens, uint32_t* row_ids,
+                       uint32_t* row_steps, uint8_t* finished, hipStream_t s);
+int decode_slots_advance(int* lens, uint32_t* row_steps, uint8_t* finished, const int* stop_lens, int B, hipStream_t s);
 }  // namespace ergm
 
 using namespace ergm;
@@ -50,6 +58,12 @@ struct ergm_decode_plan {
     const int* cap_lens;
     uint8_t* finished;
     float* logits;
+    // slot mode (ergm_decode_bind_slots): every step runs over all max_batch slots
+    bool slots;
+    int* cap_lens_rw;
+    int* stop_lens;
+    uint32_t* row_ids;
+    uint32_t* row_steps;
 };
 
 namespace {
@@ -76,6 +90,26 @@ ergm_gemm_desc gemm_desc(int M, int N, int K, int b_layout, int c_dtype, int epi
     g.aux_out = aux_out, g.ld_aux_out = aux_out ? N : 0;
     return g;
 }
+
+// ---- slot mode: the admission (ergm_decode_admit) ----------------------------------------------------------
+// The buffers of one admission of at most R packed token rows and Rc packed caption rows, carved from the caller's
+// workspace like the plan's own.
+struct AdmitWs {
+    float* h;       // [R][E] residual stream
+    __bf16* x;      // [R][E] LayerNorm output
+    __bf16* qkv;    // [R][3E]
+    __bf16* att;    // [R][E]
+    __bf16* q;      // [R][E]
+    __bf16* pre;    // [R][F]
+    __bf16* act;    // [R][F]
+    float *mean, *rstd;  // [R]
+    __bf16* cap;    // [Rc][E] caption embeddings
+    __bf16* ckv;    // [Rc][2E] caption K | V of one layer
+    float* hl;      // [max_batch][E] the last row of every sequence
+    float* lg;      // [max_batch][vocab_pad] their logits, before they go to the slots
+    void* gemm_ws;
+    size_t gemm_ws_bytes;
+};
 
 // The largest split-K workspace of the step's GEMMs over every batch size the plan can be bound to.
 size_t gemm_ws_need(const ergm_decode_dims& d) {
@@ -230,7 +264,9 @@ int walk(const ergm_decode_plan* P, Walk& w, int B, const int64_t* tokens, const
             ERGM_TRY(linear(P, w, B, d.vocab_pad, E, P->x, nullptr, nullptr, P->p.wte_b, ERGM_NK, P->logits, ERGM_EPI_NONE,
                             nullptr, nullptr, d.vocab_pad));
     }
-    if (w.on()) ERGM_TRY(decode_lens_advance(P->lens, P->finished, B, w.s));
+    if (w.on())
+        ERGM_TRY(P->slots ? decode_slots_advance(P->lens, P->row_steps, P->finished, P->stop_lens, B, w.s)
+                          : decode_lens_advance(P->lens, P->finished, B, w.s));
     return ERGM_OK;
 }
 
@@ -242,6 +278,152 @@ int step_ready(const ergm_decode_plan* P, int steps, const char* what) {
     return ERGM_OK;
 }
 
+
+// The largest split-K workspace of an admission's GEMMs: over every row count up to (R, Rc, max_batch sequences), so
+// that a workspace sized for R rows serves every smaller admission; or (n_seq > 0) of the one admission of exactly
+// R rows, Rc caption rows and n_seq sequences, which the first covers.
+size_t admit_gemm_ws_need(const ergm_decode_dims& d, int R, int Rc, int n_seq) {
+    const int E = d.n_embd, F = d.n_inner;
+    size_t need = 0;
+    auto upto = [&](int rows, int N, int K, int b_layout) {
+        for (int M = n_seq > 0 ? rows : 1; M <= rows; ++M) {
+            const ergm_gemm_desc g = gemm_desc(M, N, K, b_layout, ERGM_F32, ERGM_EPI_NONE, nullptr, nullptr, nullptr, N);
+            need = std::max(need, ergm_gemm_workspace_size(&g));
+        }
+    };
+    upto(R, 3 * E, E, ERGM_KN), upto(R, E, E, ERGM_KN), upto(R, F, E, ERGM_KN), upto(R, E, F, ERGM_KN);
+    upto(Rc, 2 * E, E, ERGM_KN);
+    upto(n_seq > 0 ? n_seq : d.max_batch, d.vocab_pad, E, ERGM_NK);
+    return need;
+}
+
+size_t admit_carve(const ergm_decode_dims& d, int R_, int Rc_, int n_seq, AdmitWs* A, char* base) {
+    const size_t R = R_, Rc = Rc_, mb = d.max_batch, E = d.n_embd, F = d.n_inner;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* p = base ? base + off : nullptr;
+        off += al256(bytes);
+        return p;
+    };
+    A->h = reinterpret_cast<float*>(take(R * E * 4));
+    A->x = reinterpret_cast<__bf16*>(take(std::max(R, mb) * E * 2));
+    A->qkv = reinterpret_cast<__bf16*>(take(R * 3 * E * 2));
+    A->att = reinterpret_cast<__bf16*>(take(R * E * 2));
+    A->q = reinterpret_cast<__bf16*>(take(R * E * 2));
+    A->pre = reinterpret_cast<__bf16*>(take(R * F * 2));
+    A->act = reinterpret_cast<__bf16*>(take(R * F * 2));
+    A->mean = reinterpret_cast<float*>(take(std::max(R, mb) * 4));
+    A->rstd = reinterpret_cast<float*>(take(std::max(R, mb) * 4));
+    A->cap = reinterpret_cast<__bf16*>(take(Rc * E * 2));
+    A->ckv = reinterpret_cast<__bf16*>(take(Rc * 2 * E * 2));
+    A->hl = reinterpret_cast<float*>(take(mb * E * 4));
+    A->lg = reinterpret_cast<float*>(take(mb * (size_t)d.vocab_pad * 4));
+    A->gemm_ws_bytes = std::max<size_t>(16, admit_gemm_ws_need(d, R_, Rc_, n_seq));
+    A->gemm_ws = take(A->gemm_ws_bytes);
+    return off;
+}
+
+// What one admission was called with; the launch sequence below reads nothing else.
+struct Admit {
+    int n_seq, R, Rc, max_n, max_c;  // sequences, packed token / caption rows, the longest of each
+    const int* meta;                 // device [ERGM_ADMIT_META_ROWS][n_seq]
+    const int64_t *ids, *tt, *cap_ids;
+    const float *vis, *aud;
+    const uint8_t* has_feat;
+    AdmitWs ws;
+    const int* row(int i) const { return meta ? meta + (size_t)i * n_seq : nullptr; }
+};
+
+int admit_ln(const ergm_decode_plan* P, Walk& w, const Admit& a, const float* in, int rows, const float* g, const float* b) {
+    if (!w.on()) return ERGM_OK;
+    return ergm_layernorm_fwd(in, g, b, a.ws.x, a.ws.mean, a.ws.rstd, rows, P->d.n_embd, P->d.eps, w.s);
+}
+
+// ergm_gemm as ops.gemm calls it, on the admission's workspace
+int admit_gemm(Walk& w, const Admit& a, int M, int N, int K, const void* A, const void* W, int b_layout, void* C, int c_dtype,
+               int epi, const float* bias, const void* aux, void* aux_out, int ldb = 0) {
+    ergm_gemm_desc g = gemm_desc(M, N, K, b_layout, c_dtype, epi, bias, aux, aux_out, N);
+    if (ldb) g.ldb = ldb;
+    int cfg = 0, split = 1, flags = 0;
+    ERGM_TRY(ergm_gemm_plan(&g, &cfg, &split, &flags));
+    if (!w.on(split > 1 ? 2 : 1)) return ERGM_OK;
+    const size_t need = ergm_gemm_workspace_size(&g);
+    ERGM_CHECK_ARG(need <= a.ws.gemm_ws_bytes, "decode_admit: GEMM workspace %zu > %zu bytes (a GEMM override set after the query)",
+                   need, a.ws.gemm_ws_bytes);
+    return ergm_gemm(&g, A, W, C, a.ws.gemm_ws, need, w.s);
+}
+
+// The admission's launch sequence, written once: a dry walk (w.dry) only counts.
+int walk_admit(const ergm_decode_plan* P, Walk& w, const Admit& a) {
+    const ergm_decode_dims& d = P->d;
+    const int E = d.n_embd, F = d.n_inner, H = d.n_head, R = a.R, Rc = a.Rc, n = a.n_seq;
+    const AdmitWs& W = a.ws;
+    const int *slot = a.row(0), *q0 = a.row(1), *qn = a.row(2), *c0 = a.row(3), *cn = a.row(4), *last = a.row(7),
+              *ones = a.row(8), *iota = a.row(9);
+    const int64_t kv_row = (int64_t)2 * E * 2;  // bytes of a K | V row
+    if (w.on())
+        ERGM_TRY(ergm_embed_packed(a.ids, a.tt, a.cap_ids, P->p.wte, P->p.wpe, a.vis, a.aud, a.has_feat, q0, qn, c0, cn, n, R, Rc,
+                                   a.max_n, a.max_c, W.h, W.cap, E, E, d.vocab_pad, d.n_positions, w.s));
+    for (int l = 0; l < d.n_layer; ++l) {
+        ERGM_TRY(admit_ln(P, w, a, W.h, R, lf(P, l, ERGM_T_LN1_W), lf(P, l, ERGM_T_LN1_W + 1)));
+        ERGM_TRY(admit_gemm(w, a, R, 3 * E, E, W.x, lb(P, l, ERGM_T_ATTN_W), ERGM_KN, W.qkv, ERGM_BF16, ERGM_EPI_BIAS,
+                            lf(P, l, ERGM_T_ATTN_W + 1), nullptr, nullptr));
+        if (w.on())
+            ERGM_TRY(ergm_attn_fwd_ragged(W.qkv, W.qkv + E, W.qkv + 2 * E, W.att, nullptr, q0, qn, q0, qn, n, H, R, R, a.max_n,
+                                          a.max_n, 3 * E, 3 * E, 3 * E, E, 1, w.s));
+        if (w.on())
+            ERGM_TRY(ergm_rows_to_slots(W.qkv + E, (int64_t)3 * E * 2, q0, qn, slot, n, R, a.max_n, P->kv[l],
+                                        (int64_t)d.max_len * kv_row, kv_row, (int)kv_row, d.max_batch, d.max_len, w.s));
+        ERGM_TRY(admit_gemm(w, a, R, E, E, W.att, lb(P, l, ERGM_T_APROJ_W), ERGM_KN, W.h, ERGM_F32, ERGM_EPI_BIAS_RESID,
+                            lf(P, l, ERGM_T_APROJ_W + 1), W.h, nullptr));
+        // layer l's columns of the stacked caption K | V weight [E][L·2E] (the view the Python path passes)
+        ERGM_TRY(admit_gemm(w, a, Rc, 2 * E, E, W.cap, reinterpret_cast<const __bf16*>(P->p.capkv_w_b) + (size_t)l * 2 * E,
+                            ERGM_KN, W.ckv, ERGM_BF16, ERGM_EPI_BIAS, P->p.capkv_b + (size_t)l * 2 * E, nullptr, nullptr,
+                            d.n_layer * 2 * E));
+        if (w.on())
+            ERGM_TRY(ergm_rows_to_slots(W.ckv, kv_row, c0, cn, slot, n, Rc, a.max_c, P->xkv[l], (int64_t)d.cap_max * kv_row,
+                                        kv_row, (int)kv_row, d.max_batch, d.cap_max, w.s));
+        ERGM_TRY(admit_ln(P, w, a, W.h, R, lf(P, l, ERGM_T_LNX_W), lf(P, l, ERGM_T_LNX_W + 1)));
+        ERGM_TRY(admit_gemm(w, a, R, E, E, W.x, lb(P, l, ERGM_T_XQ_W), ERGM_KN, W.q, ERGM_BF16, ERGM_EPI_BIAS,
+                            lf(P, l, ERGM_T_XQ_W + 1), nullptr, nullptr));
+        if (w.on())
+            ERGM_TRY(ergm_attn_fwd_ragged(W.q, W.ckv, W.ckv + E, W.att, nullptr, q0, qn, c0, cn, n, H, R, Rc, a.max_n, a.max_c, E,
+                                          2 * E, 2 * E, E, 0, w.s));
+        ERGM_TRY(admit_gemm(w, a, R, E, E, W.att, lb(P, l, ERGM_T_XPROJ_W), ERGM_KN, W.h, ERGM_F32, ERGM_EPI_BIAS_RESID,
+                            lf(P, l, ERGM_T_XPROJ_W + 1), W.h, nullptr));
+        ERGM_TRY(admit_ln(P, w, a, W.h, R, lf(P, l, ERGM_T_LN2_W), lf(P, l, ERGM_T_LN2_W + 1)));
+        ERGM_TRY(admit_gemm(w, a, R, F, E, W.x, lb(P, l, ERGM_T_FC_W), ERGM_KN, W.act, ERGM_BF16, ERGM_EPI_BIAS_GELU,
+                            lf(P, l, ERGM_T_FC_W + 1), nullptr, W.pre));
+        ERGM_TRY(admit_gemm(w, a, R, E, F, W.act, lb(P, l, ERGM_T_MPROJ_W), ERGM_KN, W.h, ERGM_F32, ERGM_EPI_BIAS_RESID,
+                            lf(P, l, ERGM_T_MPROJ_W + 1), W.h, nullptr));
+    }
+    // the last row of every sequence -> ln_f -> the head -> logits[slot]
+    if (w.on())
+        ERGM_TRY(ergm_rows_to_slots(W.h, (int64_t)E * 4, last, ones, iota, n, R, 1, W.hl, (int64_t)E * 4, (int64_t)E * 4, E * 4, n,
+                                    1, w.s));
+    ERGM_TRY(admit_ln(P, w, a, W.hl, n, P->p.ln_f_w, P->p.ln_f_b));
+    ERGM_TRY(admit_gemm(w, a, n, d.vocab_pad, E, W.x, P->p.wte_b, ERGM_NK, W.lg, ERGM_F32, ERGM_EPI_NONE, nullptr, nullptr,
+                        nullptr));
+    if (w.on())
+        ERGM_TRY(ergm_rows_to_slots(W.lg, (int64_t)d.vocab_pad * 4, iota, ones, slot, n, n, 1, P->logits, (int64_t)d.vocab_pad * 4,
+                                    (int64_t)d.vocab_pad * 4, d.vocab_pad * 4, d.max_batch, 1, w.s));
+    if (w.on())
+        ERGM_TRY(decode_slots_admit(slot, qn, cn, a.row(5), reinterpret_cast<const uint32_t*>(a.row(6)), n, d.max_batch, d.max_len,
+                                    d.cap_max, P->lens, P->cap_lens_rw, P->stop_lens, P->row_ids, P->row_steps, P->finished,
+                                    w.s));
+    return ERGM_OK;
+}
+
+int slots_ready(const ergm_decode_plan* P, const char* what) {
+    ERGM_CHECK_ARG(P, "%s: null plan", what);
+    ERGM_CHECK_ARG(P->slots, "%s: no slots bound (ergm_decode_bind_slots)", what);
+    return ERGM_OK;
+}
+
+bool admit_rows_ok(const ergm_decode_dims& d, int max_rows, int max_cap_rows) {
+    return max_rows >= 1 && max_cap_rows >= 1 && (int64_t)max_rows <= (int64_t)d.max_batch * d.max_len &&
+           (int64_t)max_cap_rows <= (int64_t)d.max_batch * d.cap_max;
+}
 }  // namespace
 
 extern "C" size_t ergm_decode_workspace_size(const ergm_decode_dims* dims) {
@@ -278,6 +460,9 @@ extern "C" int ergm_decode_create(const ergm_decode_dims* dims, const ergm_model
     P->cap_lens = nullptr;
     P->finished = nullptr;
     P->logits = nullptr;
+    P->slots = false;
+    P->cap_lens_rw = P->stop_lens = nullptr;
+    P->row_ids = P->row_steps = nullptr;
     *out = P;
     return ERGM_OK;
 }
@@ -302,6 +487,7 @@ extern "C" int ergm_decode_bind(ergm_decode_plan* P, int B, int n_max, void* con
     P->B = B, P->n_max = n_max, P->Sc = Sc;
     P->lens = lens, P->cap_lens = cap_lens, P->finished = finished, P->logits = logits;
     P->bound = true;
+    P->slots = false;
     return ERGM_OK;
 }
 
@@ -341,6 +527,115 @@ extern "C" int ergm_decode_run(ergm_decode_plan* P, int first, int n, float top_
         }
         ERGM_TRY(ergm_topp_sample(P->logits, P->d.vocab_pad, B, P->d.vocab, top_p, seed, (uint32_t)i, P->finished, eos_id,
                                   tokens_out + (size_t)i * B, nullptr, nullptr, s));
+    }
+    return ERGM_OK;
+}
+
+extern "C" int ergm_decode_bind_slots(ergm_decode_plan* P, void* const* kv, void* const* xkv, float* logits, int* lens,
+                                      int* cap_lens, uint8_t* finished, int* stop_lens, uint32_t* row_ids,
+                                      uint32_t* row_steps) {
+    ERGM_CHECK_ARG(P && kv && xkv && logits && lens && cap_lens && finished && stop_lens && row_ids && row_steps,
+                   "decode_bind_slots: null argument");
+    for (int l = 0; l < P->d.n_layer; ++l)
+        ERGM_CHECK_ARG(kv[l] && xkv[l] && aligned16(kv[l]) && aligned16(xkv[l]),
+                       "decode_bind_slots: layer %d cache pointer null or not 16-byte aligned", l);
+    ERGM_CHECK_ARG(aligned16(logits), "decode_bind_slots: logits must be 16-byte aligned");
+    P->kv.assign(kv, kv + P->d.n_layer);
+    P->xkv.assign(xkv, xkv + P->d.n_layer);
+    P->B = P->d.max_batch, P->n_max = 0, P->Sc = P->d.cap_max;
+    P->lens = lens, P->cap_lens = P->cap_lens_rw = cap_lens, P->finished = finished, P->logits = logits;
+    P->stop_lens = stop_lens, P->row_ids = row_ids, P->row_steps = row_steps;
+    P->bound = false;  // ergm_decode_step / _run serve ergm_decode_bind
+    P->slots = true;
+    return ERGM_OK;
+}
+
+extern "C" size_t ergm_decode_admit_workspace_size(const ergm_decode_dims* dims, int max_rows, int max_cap_rows) {
+    if (!dims || !dims_ok(*dims) || !admit_rows_ok(*dims, max_rows, max_cap_rows)) return 0;
+    AdmitWs A{};
+    return admit_carve(*dims, max_rows, max_cap_rows, 0, &A, nullptr);
+}
+
+extern "C" int ergm_decode_admit(ergm_decode_plan* P, int n_seq, const int* slots, const int* lens, const int* cap_lens,
+                                 const int* max_new, const int* meta, const int64_t* ids, const int64_t* token_types,
+                                 const int64_t* cap_ids, const float* vis, const float* aud, const uint8_t* has_feat,
+                                 void* workspace, size_t ws_bytes, void* stream) {
+    ERGM_TRY(slots_ready(P, "decode_admit"));
+    const ergm_decode_dims& d = P->d;
+    ERGM_CHECK_ARG(slots && lens && cap_lens && max_new && meta && ids && cap_ids && workspace, "decode_admit: null argument");
+    ERGM_CHECK_ARG(n_seq >= 1 && n_seq <= d.max_batch, "decode_admit: n_seq %d outside [1, max_batch %d]", n_seq, d.max_batch);
+    ERGM_CHECK_ARG((vis == nullptr) == (aud == nullptr), "decode_admit: visual and audio features go together");
+    ERGM_CHECK_ARG(P->p.capkv_w_b && P->p.capkv_b, "decode_admit: the plan was created without the caption K/V weights "
+                   "(capkv_w_b, capkv_b)");
+    Admit a{};
+    std::vector<char> seen(d.max_batch, 0);
+    int64_t R = 0, Rc = 0;
+    for (int b = 0; b < n_seq; ++b) {
+        ERGM_CHECK_ARG(slots[b] >= 0 && slots[b] < d.max_batch, "decode_admit: slot %d of sequence %d outside [0, max_batch %d)",
+                       slots[b], b, d.max_batch);
+        ERGM_CHECK_ARG(!seen[slots[b]], "decode_admit: slot %d named twice", slots[b]);
+        seen[slots[b]] = 1;
+        ERGM_CHECK_ARG(lens[b] >= 1, "decode_admit: sequence %d has an empty prompt (n_b %d < 1)", b, lens[b]);
+        ERGM_CHECK_ARG(cap_lens[b] >= 1, "decode_admit: sequence %d has an empty caption (c_b %d < 1)", b, cap_lens[b]);
+        ERGM_CHECK_ARG(cap_lens[b] <= d.cap_max, "decode_admit: caption of sequence %d has %d rows > cap_max %d", b, cap_lens[b],
+                       d.cap_max);
+        ERGM_CHECK_ARG(max_new[b] >= 1, "decode_admit: max_new %d of sequence %d < 1", max_new[b], b);
+        ERGM_CHECK_ARG(lens[b] <= d.max_len && max_new[b] <= d.max_len - lens[b],
+                       "decode_admit: sequence %d: n_b %d + max_new %d > max_len %d", b, lens[b], max_new[b], d.max_len);
+        R += lens[b], Rc += cap_lens[b];
+        a.max_n = std::max(a.max_n, lens[b]), a.max_c = std::max(a.max_c, cap_lens[b]);
+    }
+    ERGM_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "decode_admit: workspace must be 256-byte aligned");
+    ERGM_CHECK_ARG(admit_rows_ok(d, (int)R, (int)Rc), "decode_admit: bad row counts");
+    const size_t need = admit_carve(d, (int)R, (int)Rc, n_seq, &a.ws, nullptr);  // this admission alone
+    ERGM_CHECK_ARG(ws_bytes >= need, "decode_admit: %lld packed rows and %lld caption rows need a workspace of %zu bytes, "
+                   "%zu given", (long long)R, (long long)Rc, need, ws_bytes);
+    a.n_seq = n_seq, a.R = (int)R, a.Rc = (int)Rc;
+    a.meta = meta, a.ids = ids, a.tt = token_types, a.cap_ids = cap_ids;
+    a.vis = vis, a.aud = aud, a.has_feat = has_feat;
+    admit_carve(d, a.R, a.Rc, n_seq, &a.ws, reinterpret_cast<char*>(workspace));
+    Walk w{false};
+    w.s = as_stream(stream);
+    return walk_admit(P, w, a);
+}
+
+extern "C" int ergm_decode_admit_launches(const ergm_decode_plan* P, int n_seq, int rows, int cap_rows) {
+    ERGM_CHECK_ARG(P && n_seq >= 1 && n_seq <= P->d.max_batch && rows >= n_seq && cap_rows >= n_seq &&
+                       admit_rows_ok(P->d, rows, cap_rows),
+                   "decode_admit_launches: bad plan or counts (n_seq %d rows %d cap_rows %d)", n_seq, rows, cap_rows);
+    Admit a{};
+    a.n_seq = n_seq, a.R = rows, a.Rc = cap_rows, a.max_n = rows, a.max_c = cap_rows;
+    // buffer addresses for the GEMM descriptors the walk plans (the plan's own workspace; nothing is launched)
+    admit_carve(P->d, rows, cap_rows, n_seq, &a.ws, reinterpret_cast<char*>(P->h));
+    Walk w{true};
+    ERGM_TRY(walk_admit(P, w, a));
+    return w.count;
+}
+
+extern "C" int ergm_decode_step_slots(ergm_decode_plan* P, const int64_t* tokens, const int64_t* token_types, void* stream) {
+    ERGM_TRY(slots_ready(P, "decode_step_slots"));
+    ERGM_CHECK_ARG(tokens, "decode_step_slots: null tokens");
+    Walk w{false};
+    w.s = as_stream(stream);
+    return walk(P, w, P->d.max_batch, tokens, token_types);
+}
+
+extern "C" int ergm_decode_run_slots(ergm_decode_plan* P, int n, float top_p, uint64_t seed, int64_t eos_id, int64_t sp2_id,
+                                     int64_t* tokens_out, void* stream) {
+    ERGM_TRY(slots_ready(P, "decode_run_slots"));
+    ERGM_CHECK_ARG(n >= 1, "decode_run_slots: n %d < 1", n);
+    ERGM_CHECK_ARG(tokens_out, "decode_run_slots: null tokens_out");
+    ERGM_CHECK_ARG(top_p == top_p, "decode_run_slots: top_p is NaN");
+    hipStream_t s = as_stream(stream);
+    const int B = P->d.max_batch;
+    ERGM_TRY(decode_fill_i64(P->tt, sp2_id, B, s));
+    for (int i = 0; i < n; ++i) {
+        int64_t* tok = tokens_out + (size_t)i * B;
+        ERGM_TRY(ergm_topp_sample_rows(P->logits, P->d.vocab_pad, B, P->d.vocab, top_p, seed, P->row_ids, P->row_steps,
+                                       P->finished, eos_id, tok, nullptr, nullptr, s));
+        Walk w{false};
+        w.s = s;
+        ERGM_TRY(walk(P, w, B, tok, P->tt));
     }
     return ERGM_OK;
 }

@@ -61,6 +61,69 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
     }
 }
 
+// ergm_embed_fwd for packed rows of sequences of different lengths (ergm_embed_packed): blockIdx.z = 0 takes the token
+// rows (sequence b = blockIdx.y owns rows q_start[b] .. + q_len[b] - 1, row s of it is position s), blockIdx.z = 1
+// the caption rows (c_start / c_len).  A token row is summed in embed_fwd_kernel's order, so it is bitwise the row that
+// kernel writes for the sequence alone; lengths and starts are clamped to the packed extents (and the positions to
+// the wpe table) before an address is formed.
+template <int NV>
+__global__ __launch_bounds__(256) void embed_packed_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ tt,
+                                                           const int64_t* __restrict__ cap_ids, const float* __restrict__ wte,
+                                                           const float* __restrict__ wpe, const float* __restrict__ vis,
+                                                           const float* __restrict__ aud, const uint8_t* __restrict__ has_feat,
+                                                           const int* __restrict__ q_start, const int* __restrict__ q_len,
+                                                           const int* __restrict__ c_start, const int* __restrict__ c_len,
+                                                           int total_rows, int total_cap, int max_rows, int max_cap,
+                                                           float* __restrict__ h0, __bf16* __restrict__ cap, int ld_cap, int E,
+                                                           int V, int n_positions) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int b = blockIdx.y, s = blockIdx.x * 4 + wave;
+    if (blockIdx.z == 0) {
+        const int n = max(0, min(q_len[b], min(min(max_rows, n_positions), total_rows)));
+        if (s >= n) return;
+        const int t = max(0, min(q_start[b], total_rows - n)) + s;
+        const int64_t id = ids[t];
+        const int64_t ty = tt ? tt[t] : -1;
+        const bool ok_id = id >= 0 && id < V, ok_ty = ty >= 0 && ty < V;
+        const bool feat = vis && (!has_feat || has_feat[b]);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            int c = (i * 64 + lane) * 4;
+            if (c >= E) continue;
+            float4 x = ok_id ? *reinterpret_cast<const float4*>(wte + (size_t)id * E + c) : make_float4(0, 0, 0, 0);
+            if (feat && s == 0) {
+                float4 f = *reinterpret_cast<const float4*>(vis + (size_t)b * E + c);
+                x.x += f.x; x.y += f.y; x.z += f.z; x.w += f.w;
+            } else if (feat && s == 1) {
+                float4 f = *reinterpret_cast<const float4*>(aud + (size_t)b * E + c);
+                x.x += f.x; x.y += f.y; x.z += f.z; x.w += f.w;
+            }
+            float4 p = *reinterpret_cast<const float4*>(wpe + (size_t)s * E + c);
+            x.x += p.x; x.y += p.y; x.z += p.z; x.w += p.w;
+            if (ok_ty) {
+                float4 y = *reinterpret_cast<const float4*>(wte + (size_t)ty * E + c);
+                x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
+            }
+            *reinterpret_cast<float4*>(h0 + (size_t)t * E + c) = x;
+        }
+    } else {
+        const int n = max(0, min(c_len[b], min(max_cap, total_cap)));
+        if (s >= n) return;
+        const int t = max(0, min(c_start[b], total_cap - n)) + s;
+        const int64_t cid = cap_ids[t];
+        const bool ok_c = cid >= 0 && cid < V;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            int c = (i * 64 + lane) * 4;
+            if (c >= E) continue;
+            float4 cv = ok_c ? *reinterpret_cast<const float4*>(wte + (size_t)cid * E + c) : make_float4(0, 0, 0, 0);
+            bf16x4 cb;
+            cb[0] = f2bf(cv.x); cb[1] = f2bf(cv.y); cb[2] = f2bf(cv.z); cb[3] = f2bf(cv.w);
+            *reinterpret_cast<bf16x4*>(cap + (size_t)t * ld_cap + c) = cb;
+        }
+    }
+}
+
 constexpr int SORT_MAX = 16384;  // entries one workgroup sorts in LDS (128 KiB of u64)
 
 // keys = (vocab id << 32) | entry, entry in [0, 3T): [0,T) input ids, [T,2T) token types, [2T,3T) captions,
@@ -333,6 +396,39 @@ extern "C" int ergm_embed_fwd(const int64_t* ids, const int64_t* tt, const int64
     ERGM_TRY(check_dropout(dropout));
     return embed_fwd_ld(ids, tt, cap_ids, wte, wpe, vis, ld_vis, aud, h0, cap, E, B, S, E, V, as_stream(stream),
                         drop_site_of(dropout, E));
+}
+
+extern "C" int ergm_embed_packed(const int64_t* ids, const int64_t* tt, const int64_t* cap_ids, const float* wte,
+                                 const float* wpe, const float* vis, const float* aud, const uint8_t* has_feat,
+                                 const int* q_start, const int* q_len, const int* c_start, const int* c_len, int n_seq,
+                                 int total_rows, int total_cap, int max_rows, int max_cap, float* h0, void* cap, int ld_cap,
+                                 int E, int V, int n_positions, void* stream) {
+    ERGM_CHECK_ARG(ids && cap_ids && wte && wpe && h0 && cap && q_start && q_len && c_start && c_len,
+                   "embed_packed: null argument");
+    ERGM_CHECK_ARG(n_seq > 0 && n_seq <= 65535 && E > 0 && E % 4 == 0 && E <= 1024 && V > 0 && n_positions > 0,
+                   "embed_packed: bad shape");
+    ERGM_CHECK_ARG(total_rows > 0 && total_cap > 0 && max_rows > 0 && max_rows <= total_rows && max_cap > 0 &&
+                       max_cap <= total_cap,
+                   "embed_packed: bad extents total_rows %d total_cap %d max_rows %d max_cap %d", total_rows, total_cap,
+                   max_rows, max_cap);
+    ERGM_CHECK_ARG((vis == nullptr) == (aud == nullptr), "embed_packed: visual and audio features go together");
+    ERGM_CHECK_ARG(ld_cap >= E && ld_cap % 4 == 0, "embed_packed: bad ld_cap");
+    ERGM_CHECK_ARG(aligned16(wte) && aligned16(wpe) && aligned16(h0) && (!vis || (aligned16(vis) && aligned16(aud))),
+                   "embed_packed: 16-byte alignment");
+    const dim3 grid(cdiv(std::max(max_rows, max_cap), 4), n_seq, 2);
+    hipStream_t s = as_stream(stream);
+    auto* cb = reinterpret_cast<__bf16*>(cap);
+#define ERGM_EMBED_PACKED(NV)                                                                                           \
+    ERGM_LAUNCH(embed_packed_kernel<NV>, grid, dim3(256), 0, s, ids, tt, cap_ids, wte, wpe, vis, aud, has_feat, q_start, \
+                q_len, c_start, c_len, total_rows, total_cap, max_rows, max_cap, h0, cb, ld_cap, E, V, n_positions)
+    switch (cdiv(E, 256)) {
+        case 1: ERGM_EMBED_PACKED(1); break;
+        case 2: ERGM_EMBED_PACKED(2); break;
+        case 3: ERGM_EMBED_PACKED(3); break;
+        default: ERGM_EMBED_PACKED(4); break;
+    }
+#undef ERGM_EMBED_PACKED
+    return check_launch("embed_packed");
 }
 
 namespace ergm {

@@ -19,6 +19,11 @@ cut, multinomial over one [V] row) uses the reference's own torch calls on the d
 then per token one row per sequence through every GEMM, ``ergm_attn_decode`` over each sequence's own cache
 length (the lengths stay on the device; the kernel appends the new K/V row itself), and ``ergm_topp_sample``
 for the whole batch without a sort or a host round trip.  ``KVCacheGenerator`` is its single-sequence yardstick.
+
+``ContinuousGenerator`` serves a queue of requests on a fixed set of cache slots (in-flight batching): every step runs
+over all slots, a slot finishes on the device at eos or at the bound recorded when it was filled, and the host, looking
+once in 8 steps, retires the finished requests and prefills waiting ones into the free slots.  ``SlotScheduler`` is its
+host-only policy.
 """
 from __future__ import annotations
 
@@ -418,3 +423,439 @@ class BatchedGenerator:
             self.step(out[i], tt)
         rows = out[:done].t().cpu().tolist()
         return [r[:r.index(eos_id) + 1] if eos_id in r else r for r in rows]
+
+
+NO_REQUEST = -1
+
+
+class _Request:
+    __slots__ = ("id", "n", "c", "max_new", "payload", "tokens", "slot")
+
+    def __init__(self, rid: int, n: int, c: int, max_new: int, payload):
+        self.id, self.n, self.c, self.max_new, self.payload = rid, n, c, max_new, payload
+        self.tokens: List[int] = []
+        self.slot = NO_REQUEST
+
+
+class SlotScheduler:
+    """The host-side policy of continuous batching, with the device work behind ``backend``:
+
+    * ``backend.admit_requests(slots, requests)`` prefills the requests (``.id``, ``.n``, ``.c``, ``.max_new``,
+      ``.payload``) into the named free slots;
+    * ``backend.run_chunk(n)`` runs n sample + step rounds over every slot and returns ``(tokens, finished)``:
+      tokens as n lists of one token per slot, finished as one flag per slot, read back once;
+    * ``backend.retire(slot, request)`` (optional) is told when a request leaves its slot.
+
+    Requests wait in arrival order (FIFO) and are admitted at a look, at most ``max_admit`` sequences and
+    ``max_admit_tokens`` packed prompt rows per ``admit`` call, as many calls as fill the free slots; a request that does
+    not fit the current call waits for the next one, and nothing overtakes it.  A free slot is chosen by least recent
+    admission (ties by index), so the slots take turns.  The host looks once in ``look`` steps (8, the cadence of
+    ``BatchedGenerator.generate``): it appends the chunk's tokens to the live requests, each list ending at its first
+    eos (included) or at ``max_new_tokens``, and retires the requests that ended."""
+
+    def __init__(self, backend, max_batch: int, max_len: int, cap_max: int, max_admit: Optional[int] = None,
+                 max_admit_tokens: Optional[int] = None, look: int = 8):
+        if max_batch < 1 or max_len < 2 or cap_max < 1 or look < 1:
+            raise ValueError("max_batch, cap_max, look must be at least 1 and max_len at least 2")
+        self.backend, self.max_batch, self.max_len, self.cap_max, self.look = backend, max_batch, max_len, cap_max, look
+        self.max_admit = max_batch if max_admit is None else max_admit
+        self.max_admit_tokens = max_batch * max_len if max_admit_tokens is None else max_admit_tokens
+        if not 1 <= self.max_admit <= max_batch or self.max_admit_tokens < 1:
+            raise ValueError("max_admit must lie in [1, max_batch] and max_admit_tokens be at least 1")
+        self.queue: List[_Request] = []
+        self.live: List[Optional[_Request]] = [None] * max_batch
+        self._last_admit = [-1] * max_batch   # the admit call that last filled each slot
+        self._calls = 0
+        self._next_id = 0
+        self._active = set()                  # ids queued or live: a result is returned under its id
+        self.steps = 0                        # decode steps run so far
+        self.admissions: List[List[tuple]] = []   # per admit call: (request id, slot) pairs, for tests and tools
+
+    def submit(self, n: int, c: int, max_new_tokens: Optional[int] = None, request_id: Optional[int] = None,
+               payload=None) -> int:
+        """Queue a request with a prompt of n tokens and c caption tokens; returns its id (uint32, arrival order by
+        default).  Raises ValueError when it can never be served: it would not fit a cache or one admission."""
+        if n < 1 or c < 1:
+            raise ValueError("empty prompt or caption")
+        if n >= self.max_len:
+            raise ValueError(f"prompt of {n} tokens leaves no room in a cache of max_len {self.max_len}")
+        if c > self.cap_max:
+            raise ValueError(f"caption of {c} tokens > cap_max {self.cap_max}")
+        if n > self.max_admit_tokens:
+            raise ValueError(f"prompt of {n} tokens > max_admit_tokens {self.max_admit_tokens}")
+        if max_new_tokens is None:
+            max_new_tokens = self.max_len - n
+        if not 1 <= max_new_tokens <= self.max_len - n:
+            raise ValueError(f"max_new_tokens {max_new_tokens} outside [1, {self.max_len - n}] (max_len - the prompt)")
+        rid = self._next_id if request_id is None else request_id
+        if not 0 <= rid < 2 ** 32:
+            raise ValueError("request ids are uint32")
+        if rid in self._active:
+            raise ValueError(f"request id {rid} is already queued or running")
+        self._active.add(rid)
+        self._next_id = (rid + 1) % 2 ** 32 if request_id is None else self._next_id
+        self.queue.append(_Request(rid, n, c, max_new_tokens, payload))
+        return rid
+
+    def _admit(self) -> None:
+        while self.queue:
+            free = sorted((s for s in range(self.max_batch) if self.live[s] is None),
+                          key=lambda s: (self._last_admit[s], s))
+            batch, rows = [], 0
+            while (self.queue and len(batch) < min(self.max_admit, len(free))
+                   and rows + self.queue[0].n <= self.max_admit_tokens):
+                r = self.queue.pop(0)
+                rows += r.n
+                batch.append(r)
+            if not batch:
+                return
+            slots = free[:len(batch)]
+            self.backend.admit_requests(slots, batch)
+            for s, r in zip(slots, batch):
+                r.slot, self.live[s], self._last_admit[s] = s, r, self._calls
+            self.admissions.append([(r.id, s) for s, r in zip(slots, batch)])
+            self._calls += 1
+
+    def drain(self, eos_id: int):
+        """Run until the queue and the slots are empty, yielding (id, tokens) of each request as it retires."""
+        while self.queue or any(r is not None for r in self.live):
+            self._admit()
+            tokens, finished = self.backend.run_chunk(self.look)
+            self.steps += self.look
+            for s, r in enumerate(self.live):
+                if r is None:
+                    continue
+                done = False
+                for row in tokens:
+                    tok = int(row[s])
+                    r.tokens.append(tok)
+                    if tok == eos_id or len(r.tokens) == r.max_new:
+                        done = True
+                        break
+                if done != bool(finished[s]):
+                    raise RuntimeError(f"slot {s}: the device says finished = {int(finished[s])}, the tokens say {done}")
+                if done:
+                    self.live[s] = None
+                    self._active.discard(r.id)
+                    retire = getattr(self.backend, "retire", None)
+                    if retire is not None:
+                        retire(s, r)
+                    yield r.id, r.tokens
+
+    def run(self, eos_id: int) -> dict:
+        return dict(self.drain(eos_id))
+
+
+def _u32_as_i32(x: int) -> int:
+    return x - 2 ** 32 if x >= 2 ** 31 else x
+
+
+class ContinuousGenerator:
+    """In-flight batching over ``max_batch`` cache slots: requests are prefilled into free slots while the others keep
+    decoding, every step runs over all slots, and a request's result does not depend on what it ran beside (bitwise
+    with ``max_admit=1`` on engine "fused", whose rows are independent of their neighbours).
+
+    A prompt is (input_ids, token_type_ids, caption_ids, imgs, auds) as in ``BatchedGenerator.prefill``.  The draw of a
+    request's i-th token is ergm_topp_sample_rows' counter {request id, 0, 0xE5A3, i}: seeded runs repeat whatever the
+    slot and the neighbours.
+
+    ``engine``: "python" (default, the yardstick) admits with the kernels the static prefill uses, sequence by sequence
+    for the embedding and the attention, and drives every kernel of a step from Python; "native" / "fused" hand the
+    admission (ergm_decode_admit: packed embedding, ragged attention, rows to slots) and the sample + step chunks
+    (ergm_decode_run_slots) to the library's executor."""
+
+    ENGINES = BatchedGenerator.ENGINES
+
+    def __init__(self, model, max_batch: int, max_len: int, cap_max: int, engine: str = "python",
+                 max_admit: Optional[int] = None, max_admit_tokens: Optional[int] = None, keep_logits: bool = False):
+        if engine not in self.ENGINES:
+            raise ValueError(f"engine {engine!r} is not one of {sorted(self.ENGINES)}")
+        cfg = model.config
+        if max_len > cfg.n_positions:
+            raise ValueError(f"max_len {max_len} > n_positions {cfg.n_positions}")
+        self.engine, self.m, self.cfg = engine, model, cfg
+        self.E, self.H, self.L, self.F = cfg.n_embd, cfg.n_head, cfg.n_layer, cfg.inner
+        self.max_batch, self.max_len, self.cap_max = max_batch, max_len, cap_max
+        if max_admit_tokens is None:
+            max_admit_tokens = min(2048, max_batch * max_len)
+        self.sched = SlotScheduler(self, max_batch, max_len, cap_max, max_admit, max_admit_tokens)
+        self.keep_logits = keep_logits
+        self.final_logits: dict = {}   # keep_logits: id -> the slot's logits row [V] when the request retired
+        dev = self.dev = model.flat.device
+        E, mb, lay = self.E, max_batch, model.layout
+        self.kv = [torch.empty(mb, max_len, 2 * E, dtype=torch.bfloat16, device=dev) for _ in range(self.L)]
+        self.xkv = [torch.empty(mb, cap_max, 2 * E, dtype=torch.bfloat16, device=dev) for _ in range(self.L)]
+        self._logits = torch.zeros(mb, lay.vocab_pad, dtype=torch.float32, device=dev)
+        self.lens = torch.zeros(mb, dtype=torch.int32, device=dev)
+        self.cap_lens = torch.zeros(mb, dtype=torch.int32, device=dev)
+        self.stop_lens = torch.zeros(mb, dtype=torch.int32, device=dev)
+        self.finished = torch.ones(mb, dtype=torch.uint8, device=dev)      # every slot idle
+        self.row_ids = torch.zeros(mb, dtype=torch.int32, device=dev)      # uint32 bits
+        self.row_steps = torch.zeros(mb, dtype=torch.int32, device=dev)
+        self._ws = ops.attn_decode_workspace(mb, self.H, max(max_len, cap_max), dev)
+        self._plan = self._plan_ws = self._plan_params = self._admit_ws = None
+        self._sampling = None   # (top_p, eos_id, sp2_id, seed) of the run in progress
+        self.admit_calls = 0
+        if engine != "python":
+            self._create_plan()
+
+    _f, _b, _ln = KVCacheGenerator._f, KVCacheGenerator._b, KVCacheGenerator._ln
+    _gemm, _mlp, _head, _stream = (BatchedGenerator._gemm, BatchedGenerator._mlp, BatchedGenerator._head,
+                                   BatchedGenerator._stream)
+
+    def __del__(self):
+        try:
+            plan, self._plan = self._plan, None
+            if plan is not None:
+                L.load().ergm_decode_destroy(plan)
+        except Exception:
+            pass
+
+    @property
+    def logits(self) -> torch.Tensor:
+        """The next-token logits of every slot, [max_batch, V] (fp32)."""
+        return self._logits[:, :self.m.layout.vocab]
+
+    def _create_plan(self) -> None:
+        lib, lay = L.load(), self.m.layout
+        self.m.refresh_bf16()
+        dims = L.DecodeDims(vocab=lay.vocab, vocab_pad=lay.vocab_pad, n_embd=self.E, n_layer=self.L, n_head=self.H,
+                            n_inner=self.F, n_positions=self.cfg.n_positions, max_batch=self.max_batch,
+                            max_len=self.max_len, cap_max=self.cap_max, eps=self.cfg.layer_norm_epsilon)
+        prm = L.ModelParams()
+        prm.wte, prm.wte_b = self._f("__wte_pad").data_ptr(), self._b("__wte_pad").data_ptr()
+        prm.wpe = self._f("transformer.wpe.weight").data_ptr()
+        prm.ln_f_w = self._f("transformer.ln_f.weight").data_ptr()
+        prm.ln_f_b = self._f("transformer.ln_f.bias").data_ptr()
+        prm.capkv_w_b, prm.capkv_b = self._b("__capkv_w").data_ptr(), self._f("__capkv_b").data_ptr()
+        prm.layer_f32 = self.m.flat.data_ptr() + 4 * lay.layer_base[0]
+        prm.layer_b16 = self.m.flat_b16.data_ptr() + 2 * lay.layer_base[0]
+        prm.layer_stride = lay.layer_stride
+        for i, o in enumerate(lay.layer_off):
+            prm.layer_off[i] = o
+        need = lib.ergm_decode_workspace_size(C.byref(dims))
+        rows = min(self.sched.max_admit_tokens, self.max_batch * self.max_len)
+        need_admit = lib.ergm_decode_admit_workspace_size(C.byref(dims), rows, self.sched.max_admit * self.cap_max)
+        if need == 0 or need_admit == 0:
+            raise ValueError("the decode executor does not support this model's dimensions")
+        self._plan_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        self._admit_ws = torch.empty(need_admit, dtype=torch.uint8, device=self.dev)
+        self._plan_params = prm
+        plan = C.c_void_p()
+        L.check(lib.ergm_decode_create(C.byref(dims), C.byref(prm), C.c_void_p(self._plan_ws.data_ptr()), need,
+                                       C.byref(plan)), "ergm_decode_create")
+        self._plan = plan
+        L.call("ergm_decode_set_engine", plan, self.ENGINES[self.engine])
+        ptrs = C.c_void_p * self.L
+        p = lambda t: C.c_void_p(t.data_ptr())
+        L.call("ergm_decode_bind_slots", plan, ptrs(*[t.data_ptr() for t in self.kv]),
+               ptrs(*[t.data_ptr() for t in self.xkv]), p(self._logits), p(self.lens), p(self.cap_lens), p(self.finished),
+               p(self.stop_lens), p(self.row_ids), p(self.row_steps))
+
+    def admit_launches(self, n_seq: int, rows: int, cap_rows: int) -> int:
+        """Kernel launches of one native admission of these sizes (ergm_decode_admit_launches)."""
+        if self._plan is None:
+            raise ValueError("the python engine has no executor plan")
+        n = L.load().ergm_decode_admit_launches(self._plan, n_seq, rows, cap_rows)
+        if n < 0:
+            L.check(n, "ergm_decode_admit_launches")
+        return n
+
+    # ---- admission --------------------------------------------------------------------------------------
+    def _features(self, prompts):
+        """(vis, aud) f32 [n_seq, E], projected when the features are wider or narrower than E (config 5), zeros for
+        the sequences without features, and the per-sequence flags; (None, None, flags) when no prompt has features."""
+        has = [p[3] is not None for p in prompts]
+        if not any(has):
+            return None, None, has
+        n, Fd, dev = len(prompts), self.m.layout.Fd, self.dev
+        vis = torch.zeros(n, Fd, dtype=torch.float32, device=dev)
+        aud = torch.zeros(n, Fd, dtype=torch.float32, device=dev)
+        for b, p in enumerate(prompts):
+            if has[b]:
+                vis[b] = p[3].float().reshape(-1, Fd)[0]
+                aud[b] = p[4].float().reshape(Fd)
+        if Fd != self.E:
+            vis, aud = (self._gemm(x.to(torch.bfloat16), f"transformer.{m}", n, self.E, Fd, out_dtype=torch.float32,
+                                   epilogue=L.EPI_BIAS) for x, m in ((vis, "visual_proj"), (aud, "audio_proj")))
+        return vis, aud, has
+
+    @torch.no_grad()
+    def admit(self, slots, prompts, max_new_tokens=None, request_ids=None) -> None:
+        """Prefill ``prompts`` into the free ``slots`` (low level; ``submit`` / ``run`` do this through the scheduler).
+        max_new_tokens: one bound per prompt (default: to the end of the cache); request_ids: the uint32 ids the
+        draws are keyed by (default 0 .. n-1)."""
+        self.m.refresh_bf16()
+        n_seq = len(prompts)
+        slots = [int(s) for s in slots]
+        ids_l = [p[0].reshape(-1) for p in prompts]
+        tt_l = [p[1].reshape(-1) for p in prompts]
+        cap_l = [p[2].reshape(-1) for p in prompts]
+        lens = [int(t.numel()) for t in ids_l]
+        clens = [int(t.numel()) for t in cap_l]
+        max_new = [self.max_len - n for n in lens] if max_new_tokens is None else [int(x) for x in max_new_tokens]
+        rids = list(range(n_seq)) if request_ids is None else [int(x) for x in request_ids]
+        if not (n_seq == len(slots) == len(max_new) == len(rids)) or n_seq < 1:
+            raise ValueError("admit takes one slot, one bound and one id per prompt")
+        if len(set(slots)) != n_seq or min(slots) < 0 or max(slots) >= self.max_batch:
+            raise ValueError(f"slots {slots}: outside [0, {self.max_batch}) or named twice")
+        for n, c, k in zip(lens, clens, max_new):
+            if n < 1 or c < 1 or c > self.cap_max or k < 1 or n + k > self.max_len:
+                raise ValueError(f"a prompt of {n} tokens, {c} caption tokens and {k} new tokens does not fit "
+                                 f"max_len {self.max_len} / cap_max {self.cap_max}")
+        if sum(lens) > self.sched.max_admit_tokens or n_seq > self.sched.max_admit:
+            raise ValueError("more sequences or packed rows than one admission takes (max_admit, max_admit_tokens)")
+        vis, aud, has = self._features(prompts)
+        q0 = [sum(lens[:b]) for b in range(n_seq)]
+        c0 = [sum(clens[:b]) for b in range(n_seq)]
+        self.admit_calls += 1
+        if self.engine == "python":
+            self._admit_python(slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has)
+        else:
+            self._admit_native(slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has)
+
+    def _admit_python(self, slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has) -> None:
+        E, H, dev, n_seq = self.E, self.H, self.dev, len(slots)
+        R, Rc = sum(lens), sum(clens)
+        wte, wpe = self._f("__wte_pad"), self._f("transformer.wpe.weight")
+        h = torch.empty(R, E, dtype=torch.float32, device=dev)
+        cap = torch.empty(Rc, E, dtype=torch.bfloat16, device=dev)
+        rows = [slice(q0[b], q0[b] + lens[b]) for b in range(n_seq)]
+        crows = [slice(c0[b], c0[b] + clens[b]) for b in range(n_seq)]
+        for b in range(n_seq):
+            ids, cids = ids_l[b].view(1, -1), cap_l[b].view(1, -1)
+            v, a = (vis[b:b + 1], aud[b:b + 1]) if has[b] else (None, None)
+            h[rows[b]], _ = ops.embed_fwd(ids, tt_l[b].view(1, -1), ids, wte, wpe, v, a)
+            _, cap[crows[b]] = ops.embed_fwd(cids, None, cids, wte, wpe)
+        for l in range(self.L):
+            p = f"transformer.h.{l}."
+            x = self._ln(h, p + "ln_1")
+            qkv = self._gemm(x, p + "attn.c_attn", R, 3 * E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+            a = torch.empty(R, E, dtype=torch.bfloat16, device=dev)
+            for b, r in enumerate(rows):
+                ops.attn_fwd(qkv[r, :E], qkv[r, E:2 * E], qkv[r, 2 * E:], 1, H, lens[b], lens[b], True, o=a[r])
+                self.kv[l][slots[b], :lens[b]].copy_(qkv[r, E:])
+            self._gemm(a, p + "attn.c_proj", R, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
+            ckv = self._gemm(cap, p + "crossattention.c_attn", Rc, 2 * E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+            for b, cr in enumerate(crows):
+                self.xkv[l][slots[b], :clens[b]].copy_(ckv[cr])
+            x = self._ln(h, p + "ln_cross_attn")
+            q = self._gemm(x, p + "crossattention.q_attn", R, E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+            a = torch.empty(R, E, dtype=torch.bfloat16, device=dev)
+            for b, (r, cr) in enumerate(zip(rows, crows)):
+                ops.attn_fwd(q[r], ckv[cr, :E], ckv[cr, E:], 1, H, lens[b], clens[b], False, o=a[r])
+            self._gemm(a, p + "crossattention.c_proj", R, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
+            self._mlp(p, h, R)
+        last = torch.tensor([q0[b] + lens[b] - 1 for b in range(n_seq)], device=dev)
+        sl = torch.tensor(slots, device=dev)
+        self._logits[sl] = self._head(h.index_select(0, last))
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+        self.lens[sl] = i32(lens)
+        self.cap_lens[sl] = i32(clens)
+        self.stop_lens[sl] = i32([n + k for n, k in zip(lens, max_new)])
+        self.row_ids[sl] = i32([_u32_as_i32(r) for r in rids])
+        self.row_steps[sl] = 0
+        self.finished[sl] = 0
+
+    def _admit_native(self, slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has) -> None:
+        dev, n_seq = self.dev, len(slots)
+        meta = torch.tensor([slots, q0, lens, c0, clens, max_new, [_u32_as_i32(r) for r in rids],
+                             [a + n - 1 for a, n in zip(q0, lens)], [1] * n_seq, list(range(n_seq))],
+                            dtype=torch.int32).to(dev)
+        ids = torch.cat(ids_l).to(device=dev, dtype=torch.int64)
+        tt = torch.cat(tt_l).to(device=dev, dtype=torch.int64)
+        cids = torch.cat(cap_l).to(device=dev, dtype=torch.int64)
+        flags = None if vis is None else torch.tensor(has, dtype=torch.uint8).to(dev)
+        arr = lambda v: (C.c_int * n_seq)(*v)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        L.call("ergm_decode_admit", self._plan, n_seq, arr(slots), arr(lens), arr(clens), arr(max_new), p(meta), p(ids), p(tt),
+               p(cids), p(vis), p(aud), p(flags), p(self._admit_ws), self._admit_ws.numel(), self._stream())
+
+    # ---- decode -------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, tokens: torch.Tensor, token_types: torch.Tensor) -> torch.Tensor:
+        """Append one token per slot (int64 [max_batch] on the device; what an idle or finished slot gets does not
+        matter) and return the logits [max_batch, V].  A live row's length and draw counter advance by one, and it
+        finishes when it reaches the bound of its admission."""
+        B, E = self.max_batch, self.E
+        tokens, token_types = tokens.reshape(-1), token_types.reshape(-1)
+        if tokens.numel() != B or token_types.numel() != B:
+            raise ValueError(f"step takes one token and one token type per slot ({B})")
+        if tokens.dtype != torch.int64 or token_types.dtype != torch.int64 or not (tokens.is_cuda and token_types.is_cuda):
+            raise ValueError("step takes int64 GPU tensors")
+        if self.engine != "python":
+            tokens, token_types = tokens.contiguous(), token_types.contiguous()
+            L.call("ergm_decode_step_slots", self._plan, C.c_void_p(tokens.data_ptr()),
+                   C.c_void_p(token_types.data_ptr()), self._stream())
+            return self.logits
+        lens, cap_lens = self.lens, self.cap_lens
+        h = ops.embed_rows(tokens, token_types, lens, self._f("__wte_pad"), self._f("transformer.wpe.weight"))
+        for l in range(self.L):
+            p = f"transformer.h.{l}."
+            x = self._ln(h, p + "ln_1")
+            qkv = self._gemm(x, p + "attn.c_attn", B, 3 * E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+            cache = self.kv[l]
+            a = ops.attn_decode(qkv, cache[:, :, :E], cache[:, :, E:], lens, True, ws=self._ws)
+            self._gemm(a, p + "attn.c_proj", B, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
+            x = self._ln(h, p + "ln_cross_attn")
+            q = self._gemm(x, p + "crossattention.q_attn", B, E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+            xkv = self.xkv[l]
+            a = ops.attn_decode(q, xkv[:, :, :E], xkv[:, :, E:], cap_lens, False, ws=self._ws)
+            self._gemm(a, p + "crossattention.c_proj", B, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
+            self._mlp(p, h, B)
+        self._logits.copy_(self._head(h))
+        live = self.finished == 0
+        lens.add_(live.to(torch.int32))
+        self.row_steps.add_(live.to(torch.int32))
+        self.finished.logical_or_(live & (lens >= self.stop_lens))
+        return self.logits
+
+    @torch.no_grad()
+    def run_chunk(self, n: int):
+        """n rounds of ergm_topp_sample_rows + one step over every slot; one read of the tokens and flags."""
+        top_p, eos_id, sp2_id, seed = self._sampling
+        B = self.max_batch
+        out = torch.empty(n, B, dtype=torch.int64, device=self.dev)
+        if self.engine != "python":
+            L.call("ergm_decode_run_slots", self._plan, n, float(top_p), seed & (2 ** 64 - 1), eos_id, sp2_id,
+                   C.c_void_p(out.data_ptr()), self._stream())
+        else:
+            tt = torch.full((B,), sp2_id, dtype=torch.int64, device=self.dev)
+            for i in range(n):
+                ops.topp_sample_rows(self._logits, self.m.layout.vocab, top_p, seed, self.row_ids, self.row_steps, eos_id,
+                                     finished=self.finished, tokens=out[i])
+                self.step(out[i], tt)
+        both = torch.cat([out.reshape(-1), self.finished.to(torch.int64)]).cpu()
+        return both[:n * B].view(n, B).tolist(), both[n * B:].tolist()
+
+    def admit_requests(self, slots, requests) -> None:
+        self.admit(slots, [r.payload for r in requests], [r.max_new for r in requests], [r.id for r in requests])
+
+    def retire(self, slot: int, request) -> None:
+        if self.keep_logits:
+            self.final_logits[request.id] = self.logits[slot].clone()
+
+    # ---- requests -----------------------------------------------------------------------------------------
+    def submit(self, prompt, max_new_tokens: Optional[int] = None, request_id: Optional[int] = None) -> int:
+        """Queue a prompt; returns its id (uint32; arrival order unless given)."""
+        return self.sched.submit(int(prompt[0].numel()), int(prompt[2].numel()), max_new_tokens, request_id, prompt)
+
+    def drain(self, top_p: float, eos_id: int, sp2_id: int, seed: int = 0):
+        """Serve the queue, yielding (id, tokens) as each request retires."""
+        self._sampling = (top_p, eos_id, sp2_id, seed)
+        try:
+            yield from self.sched.drain(eos_id)
+        finally:
+            self._sampling = None
+
+    def run(self, top_p: float, eos_id: int, sp2_id: int, seed: int = 0) -> dict:
+        """Serve the queue; returns {id: tokens}, each list ending at its first eos (included) or at its bound."""
+        return dict(self.drain(top_p, eos_id, sp2_id, seed))
+
+    def generate(self, prompts, top_p: float, eos_id: int, sp2_id: int, seed: int = 0, max_new_tokens=None) -> List[List[int]]:
+        """One token list per prompt, in submission order.  max_new_tokens: None, one bound for all, or one per prompt."""
+        if max_new_tokens is None or isinstance(max_new_tokens, int):
+            max_new_tokens = [max_new_tokens] * len(prompts)
+        ids = [self.submit(p, k) for p, k in zip(prompts, max_new_tokens)]
+        out = self.run(top_p, eos_id, sp2_id, seed)
+        return [out[i] for i in ids]

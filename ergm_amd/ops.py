@@ -386,6 +386,86 @@ def topp_sample(logits, V: int, top_p: float, seed: int, step: int, eos_id: int,
     return tokens
 
 
+def attn_fwd_ragged(q, k, v, q_start, q_len, k_start, k_len, H: int, max_q: int, max_k: int, causal: bool, o=None,
+                    lse=None):
+    """Inference attention over packed sequences of different lengths in one launch (ergm_attn_fwd_ragged).  q / o:
+    [total_q, ld] bf16 rows, k / v: [total_k, ld]; q_start / q_len / k_start / k_len: int32 [n_seq] on the device;
+    max_q / max_k: the host's bounds on the lengths.  ``lse`` (optional, f32 [H·total_q]) holds sequence b's
+    [H, q_len[b]] block at H·q_start[b].  Returns ``o``."""
+    _need_gpu(q, k, v, q_start, q_len, k_start, k_len)
+    assert q.dtype == k.dtype == v.dtype == torch.bfloat16
+    for t in (q_start, q_len, k_start, k_len):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == q_start.numel()
+    dev = q.device
+    if o is None:
+        o = torch.empty(q.shape[0], H * 64, dtype=torch.bfloat16, device=dev)
+    L.call("ergm_attn_fwd_ragged", _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _ptr(q_start), _ptr(q_len), _ptr(k_start),
+           _ptr(k_len), q_start.numel(), H, q.shape[0], k.shape[0], max_q, max_k, q.stride(0), k.stride(0), v.stride(0),
+           o.stride(0), int(bool(causal)), _stream(dev))
+    return o
+
+
+def rows_to_slots(src, start, length, slot, max_rows: int, dst, n_slots: Optional[int] = None,
+                  slot_rows: Optional[int] = None):
+    """Row t < length[b] of sequence b (row start[b] + t of ``src`` [rows, width]) -> dst[slot[b], t] (ergm_rows_to_slots).
+    ``dst``: [n_slots, slot_rows, width] (or [n_slots, width] with one row per slot), the same dtype as ``src``, rows
+    of a multiple of 16 bytes; start / length / slot int32 [n_seq] on the device; max_rows the host's bound on length."""
+    _need_gpu(src, start, length, slot, dst)
+    assert src.dtype == dst.dtype and src.dim() == 2 and src.stride(1) == 1 and dst.stride(-1) == 1
+    for t in (start, length, slot):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == start.numel()
+    es = src.element_size()
+    if dst.dim() == 2:
+        ld_slot, ld_row, rows = dst.stride(0), dst.stride(0), 1
+    else:
+        ld_slot, ld_row, rows = dst.stride(0), dst.stride(1), dst.shape[1]
+    if src.shape[1] != dst.shape[-1]:
+        raise ValueError("rows_to_slots: src and dst rows differ in width")
+    L.call("ergm_rows_to_slots", _ptr(src), src.stride(0) * es, _ptr(start), _ptr(length), _ptr(slot), start.numel(),
+           src.shape[0], max_rows, _ptr(dst), ld_slot * es, ld_row * es, src.shape[1] * es,
+           dst.shape[0] if n_slots is None else n_slots, rows if slot_rows is None else slot_rows, _stream(src.device))
+    return dst
+
+
+def embed_packed(ids, tt, cap_ids, wte, wpe, q_start, q_len, c_start, c_len, max_rows: int, max_cap: int, vis=None,
+                 aud=None, has_feat=None):
+    """ergm_embed_fwd for packed rows (ergm_embed_packed): ids / tt int64 [Σ n_b], cap_ids int64 [Σ c_b], the starts
+    and lengths int32 [n_seq] on the device, vis / aud f32 [n_seq, E] (projected) or None, has_feat uint8 [n_seq] or
+    None.  Returns (h0 f32 [Σ n_b, E], cap bf16 [Σ c_b, E])."""
+    _need_gpu(ids, cap_ids, wte, wpe, q_start, q_len, c_start, c_len)
+    assert ids.dtype == torch.int64 and cap_ids.dtype == torch.int64 and (tt is None or tt.dtype == torch.int64)
+    assert has_feat is None or has_feat.dtype == torch.uint8
+    V, E = wte.shape
+    n_seq = q_start.numel()
+    if vis is not None:
+        vis, aud = vis.contiguous(), aud.contiguous()
+        assert vis.shape == aud.shape == (n_seq, E) and vis.dtype == aud.dtype == torch.float32
+    R, Rc = ids.numel(), cap_ids.numel()
+    h0 = torch.empty(R, E, dtype=torch.float32, device=ids.device)
+    cap = torch.empty(Rc, E, dtype=torch.bfloat16, device=ids.device)
+    L.call("ergm_embed_packed", _ptr(ids), _ptr(tt), _ptr(cap_ids), _ptr(wte), _ptr(wpe), _ptr(vis), _ptr(aud),
+           _ptr(has_feat), _ptr(q_start), _ptr(q_len), _ptr(c_start), _ptr(c_len), n_seq, R, Rc, max_rows, max_cap,
+           _ptr(h0), _ptr(cap), E, E, V, wpe.shape[0], _stream(ids.device))
+    return h0, cap
+
+
+def topp_sample_rows(logits, V: int, top_p: float, seed: int, row_ids, row_steps, eos_id: int, finished=None,
+                     tokens=None, kept=None, kept_mass=None):
+    """ergm_topp_sample with the Philox counter {row_ids[b], 0, 0xE5A3, row_steps[b]} per row (ergm_topp_sample_rows):
+    row_ids / row_steps uint32 [B] on the device, passed as int32 tensors holding the same bits."""
+    _need_gpu(logits, row_ids, row_steps)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    assert finished is None or finished.dtype == torch.uint8
+    B = logits.shape[0]
+    for t in (row_ids, row_steps):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
+    if tokens is None:
+        tokens = torch.empty(B, dtype=torch.int64, device=logits.device)
+    L.call("ergm_topp_sample_rows", _ptr(logits), logits.stride(0), B, V, float(top_p), seed & (2 ** 64 - 1), _ptr(row_ids),
+           _ptr(row_steps), _ptr(finished), eos_id, _ptr(tokens), _ptr(kept), _ptr(kept_mass), _stream(logits.device))
+    return tokens
+
+
 def feat_pool(x: torch.Tensor, lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """Mean over frames of encoder outputs x [B, T, D] (f32 / bf16, any row strides with unit
     last-dim stride) -> [B, D] f32; ``lengths`` [B] int32 limits each sample to its valid frames.

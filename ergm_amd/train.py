@@ -105,6 +105,41 @@ class Trainer:
         self.model.eval()
         return self._pass(loader, False)
 
+    @torch.no_grad()
+    def test(self, loader, top_p: float, eos_id: int, sp2_id: int, seed: int = 0, max_batch: int = 8,
+             max_len: Optional[int] = None, engine: str = "python"):
+        """The reference's ``test()`` (src/main.py:291-335) without the tokenizer: one sampled response for every
+        sample of ``loader``, all of them served by one ``ContinuousGenerator`` of ``max_batch`` slots.  A sample's
+        prompt is its first n tokens, n = the count of tokens that are not ``eos_id`` (the collate pads with eos), with
+        its token types, its caption row and its visual / audio features; its draws are keyed by its index in the
+        loader, so seeded runs repeat.  Returns (hypothesis ids, reference ids = ``labels != -100``, emotion labels, the
+        per-batch LM losses of the inference forward ``validation`` runs), lists in loader order.  Decoding the ids
+        to text is the caller's."""
+        from .generate import ContinuousGenerator
+        self.model.eval()
+        dev = self.device
+        prompts, refs, emos, losses = [], [], [], []
+        for batch in DevicePrefetcher(loader, dev):
+            ids, tts, labels, caps = batch["input_ids"], batch["token_type_ids"], batch["labels"], batch["caption_ids"]
+            imgs, auds = batch.get("visual_feat"), batch.get("audio_feat")
+            n_in = (ids != eos_id).sum(1).tolist()
+            for i, n in enumerate(n_in):
+                prompts.append((ids[i, :n], tts[i, :n], caps[i], None if imgs is None else imgs[i],
+                                None if auds is None else auds[i]))
+                refs.append(labels[i][labels[i] != -100].tolist())
+            emos.extend(batch["emotion_labels"].tolist())
+            out = self.model(input_ids=ids, token_type_ids=tts, labels=labels, emotion_labels=batch["emotion_labels"],
+                             caption_ids=caps, imgs=imgs, auds=auds)
+            losses.append(out.loss_lm.detach())
+        if not prompts:
+            return [], [], [], []
+        if max_len is None:
+            max_len = self.model.config.n_positions
+        gen = ContinuousGenerator(self.model, max_batch=max_batch, max_len=max_len,
+                                  cap_max=max(int(p[2].numel()) for p in prompts), engine=engine)
+        hyps = gen.generate(prompts, top_p, eos_id, sp2_id, seed)
+        return hyps, refs, emos, [float(x) for x in torch.stack(losses).tolist()]
+
     def train(self, train_loader, valid_loader, num_epochs: int, log=print,
               seed: Optional[int] = None) -> Tuple[EpochStats, EpochStats]:
         """src/main.py:125-204: epochs of training + validation, keeping the best-PPL checkpoint.  ``seed``: as the

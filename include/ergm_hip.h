@@ -23,7 +23,8 @@
  *   ergm_xent_fwd_bwd     CrossEntropyLoss(ignore_index=-100) on shifted logits (src/model.py:704-708)
  *   ergm_emotion_head     emotion_head + its CrossEntropyLoss (src/model.py:700-701,710-711)
  *   ergm_adamw_step       torch.optim.AdamW.step (src/main.py:68,155)
- *   ergm_attn_decode, ergm_embed_rows, ergm_topp_sample
+ *   ergm_attn_decode, ergm_embed_rows, ergm_topp_sample,
+ *   ergm_attn_fwd_ragged, ergm_embed_packed, ergm_rows_to_slots, ergm_topp_sample_rows
  *                         the per-token work of nucleus_sampling (src/main.py:253-282), for a batch
  *   ergm_linear_rows      Conv1D / lm_head for the few rows of a decode step, with the nn.LayerNorm in front
  *                         of it (src/model.py:298,318,332) computed in the same launch
@@ -232,6 +233,21 @@ int ergm_quant_weight_mx(const void* W, int ldw, int K, int N, void* Wt, int ldt
 int ergm_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H,
                   int Sq, int Sk, int ldq, int ldk, int ldv, int ldo, int causal,
                   const ergm_dropout* dropout, void* keep_bits, void* stream);
+/* Inference attention over a packed batch of sequences of different lengths, one launch (no dropout; lse optional).
+ * Sequence b < n_seq owns query rows q_start[b] .. q_start[b] + q_len[b] - 1 of q [total_q][ldq] and o [total_q][ldo],
+ * and key rows k_start[b] .. k_start[b] + k_len[b] - 1 of k / v [total_k][ld]; nothing is padded.  Self-attention of
+ * a packed qkv buffer passes the same starts and lengths for both with causal = 1 (k_len[b] == q_len[b]); cross-
+ * attention the caption rows' own arrays with causal = 0.  The four arrays are device ints; max_q / max_k are the
+ * host's bounds on q_len / k_len (max_q sizes the grid: (ceil(max_q / 64), H, n_seq) workgroups, those past a
+ * sequence's last query tile exit at once).  Every value read from the arrays is clamped to [0, max] and to the
+ * packed extents before an address is formed, and no row outside a sequence's own query rows is written.  Query
+ * tiles are counted from each sequence's first row and run ergm_attn_fwd's tile loop, so the rows of sequence b are
+ * bitwise ergm_attn_fwd(B = 1, Sq = q_len[b], Sk = k_len[b]) on that sequence alone.  lse (may be NULL): f32, the
+ * [H][q_len[b]] block of sequence b at lse + H·q_start[b].                                                      */
+int ergm_attn_fwd_ragged(const void* q, const void* k, const void* v, void* o, float* lse, const int* q_start,
+                         const int* q_len, const int* k_start, const int* k_len, int n_seq, int H, int total_q,
+                         int total_k, int max_q, int max_k, int ldq, int ldk, int ldv, int ldo, int causal,
+                         void* stream);
 /* delta workspace: B*H*Sq floats.  dq/dk/dv are bf16 with their own leading dims.              */
 int ergm_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,
                   const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int H, int Sq,
@@ -336,6 +352,32 @@ int ergm_embed_rows(const int64_t* ids, const int64_t* tt, const int* pos, const
  * kept share of the row's probability) are optional outputs, 0 for a finished row.                          */
 int ergm_topp_sample(const float* logits, int ldl, int B, int V, float top_p, uint64_t seed, uint32_t step,
                      void* finished, int64_t eos_id, int64_t* tokens, int* kept, float* kept_mass, void* stream);
+/* ergm_topp_sample with a Philox counter per row: {row_ids[b], 0, 0xE5A3, row_steps[b]} (device uint32 [B] each), so
+ * a row's draws follow the request it serves and the tokens that request has drawn, not the row it happens to occupy.
+ * With row_ids = 0 .. B-1 and every row_steps[b] = step every output is bitwise ergm_topp_sample's.               */
+int ergm_topp_sample_rows(const float* logits, int ldl, int B, int V, float top_p, uint64_t seed,
+                          const uint32_t* row_ids, const uint32_t* row_steps, void* finished, int64_t eos_id,
+                          int64_t* tokens, int* kept, float* kept_mass, void* stream);
+/* Packed rows into per-slot buffers: row t < len[b] of sequence b (row start[b] + t of src, ld_src bytes apart) is
+ * copied to dst + slot[b]·ld_slot + t·ld_row (bytes), row_bytes bytes in 16-byte pieces.  start / len / slot: device
+ * int [n_seq]; total_rows = the rows of src, max_rows = the host's bound on len (it sizes the grid).  len is clamped
+ * to [0, min(max_rows, slot_rows)], start to the rows of src, and a sequence whose slot lies outside [0, n_slots)
+ * writes nothing.  Moves K | V rows into the caches, caption K | V rows, and f32 logits rows (slot_rows = 1).      */
+int ergm_rows_to_slots(const void* src, int64_t ld_src, const int* start, const int* len, const int* slot, int n_seq,
+                       int total_rows, int max_rows, void* dst, int64_t ld_slot, int64_t ld_row, int row_bytes,
+                       int n_slots, int slot_rows, void* stream);
+/* ergm_embed_fwd for packed rows of n_seq sequences of different lengths: token row s < q_len[b] of sequence b (packed
+ * row q_start[b] + s of ids / tt / h0) is ((wte[id] + [s==0]·vis[b] + [s==1]·aud[b]) + wpe[s]) + wte[tt], in that
+ * kernel's summation order: bitwise the row ergm_embed_fwd(B = 1, S = q_len[b]) writes.  Caption row s < c_len[b]
+ * (packed row c_start[b] + s of cap_ids / cap) is bf16(wte[cap_id]).  vis / aud: f32 [n_seq][E] (already projected)
+ * or both NULL; has_feat (uint8 [n_seq], may be NULL = all) marks the sequences they apply to.  The starts and
+ * lengths are device ints, clamped to max_rows / max_cap (host bounds, sizing the grid), n_positions and the packed
+ * extents; ids outside [0, V) contribute zeros and tt may be NULL, as in ergm_embed_fwd.                          */
+int ergm_embed_packed(const int64_t* ids, const int64_t* tt, const int64_t* cap_ids, const float* wte,
+                      const float* wpe, const float* vis, const float* aud, const uint8_t* has_feat,
+                      const int* q_start, const int* q_len, const int* c_start, const int* c_len, int n_seq,
+                      int total_rows, int total_cap, int max_rows, int max_cap, float* h0, void* cap, int ld_cap,
+                      int E, int V, int n_positions, void* stream);
 /* Feature pooling (data_process/feature_extraction.py:63,69: torch.mean(last_hidden_state, dim=1) of the
  * wav2vec2 / BLIP-vision encoder outputs): out[b][d] = mean_{t < len_b} x[b][t][d], x f32 or bf16 with
  * strides ld_t (frames) and ld_b (samples) in elements, lengths optional (NULL = all T frames; padded
@@ -632,7 +674,7 @@ typedef struct {
  * 1 <= max_len <= n_positions, max_batch, cap_max, n_layer >= 1.                                              */
 size_t ergm_decode_workspace_size(const ergm_decode_dims* dims);
 /* params: only the forward pointers are read (wte, wte_b, wpe, ln_f_w, ln_f_b, layer_f32, layer_b16, layer_stride,
- * layer_off).  workspace: 256-byte aligned, ws_bytes >= ergm_decode_workspace_size(dims).                       */
+ * layer_off; capkv_w_b and capkv_b by ergm_decode_admit only, which refuses a plan created without them).  workspace: 256-byte aligned, ws_bytes >= ergm_decode_workspace_size(dims).                       */
 int ergm_decode_create(const ergm_decode_dims* dims, const ergm_model_params* params, void* workspace,
                        size_t ws_bytes, ergm_decode_plan** out_plan);
 int ergm_decode_destroy(ergm_decode_plan* plan);
@@ -667,6 +709,50 @@ int ergm_decode_run(ergm_decode_plan* plan, int first, int n, float top_p, uint6
  * GEMM / attention plans as they stand now: counted by walking the step's own launch sequence dry.  Host only;
  * negative ergm_status on a bad argument.                                                                          */
 int ergm_decode_launches(const ergm_decode_plan* plan, int engine);
+/* Slot mode (continuous batching): the plan's max_batch cache slots stay bound for its life, every step runs over all
+ * of them, and sequences enter free slots between steps (ergm_decode_admit) while the others keep decoding.
+ *   kv[l] bf16 [max_batch][max_len][2·n_embd], xkv[l] bf16 [max_batch][cap_max][2·n_embd], logits f32
+ *   [max_batch][vocab_pad]; lens, cap_lens, stop_lens int [max_batch]; finished uint8 [max_batch]; row_ids, row_steps
+ *   uint32 [max_batch] (ergm_topp_sample_rows' counters: the request a slot serves and the tokens it has drawn).
+ * An idle slot holds finished = 1, lens = 0, cap_lens = 0 (the caller initialises all slots so): its cross-attention
+ * writes zeros and its self-attention append lands in row 0 of a cache nobody reads.  After this bind
+ * ergm_decode_step / _run refuse (they serve ergm_decode_bind), and the other way round.                          */
+int ergm_decode_bind_slots(ergm_decode_plan* plan, void* const* kv, void* const* xkv, float* logits, int* lens,
+                           int* cap_lens, uint8_t* finished, int* stop_lens, uint32_t* row_ids, uint32_t* row_steps);
+#define ERGM_ADMIT_META_ROWS 10
+/* Bytes of device workspace of one ergm_decode_admit of at most max_rows packed token rows and max_cap_rows packed
+ * caption rows; host only, 0 for dimensions or row counts it rejects.                                              */
+size_t ergm_decode_admit_workspace_size(const ergm_decode_dims* dims, int max_rows, int max_cap_rows);
+/* The prefill of n_seq new sequences into the named slots, enqueued on `stream` between decode steps:
+ * ergm_embed_packed; per layer ergm_layernorm_fwd / ergm_gemm (split_k = 0) over the packed rows, ragged causal
+ * attention, K | V rows to the slots, the caption K | V GEMM over the packed caption rows and its rows to the slots,
+ * ragged cross-attention, the MLP; then the last row of every sequence through ln_f and the head into logits[slot];
+ * then one kernel sets lens = n_b, cap_lens = c_b, stop_lens = n_b + max_new, row_ids = the request id, row_steps = 0,
+ * finished = 0 of every slot filled.  The same kernels with the same arguments on both engines.
+ *   slots, lens, cap_lens, max_new: HOST int [n_seq], checked here; ERGM_EINVAL before any launch for a slot outside
+ *     [0, max_batch) or named twice, n_b < 1, c_b < 1, c_b > cap_max, max_new < 1, n_b + max_new > max_len, or more
+ *     packed rows than the workspace holds.
+ *   meta: DEVICE int [ERGM_ADMIT_META_ROWS][n_seq], what the kernels read (each value clamped before use): rows
+ *     0 slot, 1 first packed token row, 2 n_b, 3 first packed caption row, 4 c_b, 5 max_new, 6 request id (uint32),
+ *     7 last packed token row (row 1 + row 2 - 1), 8 all ones, 9 0 .. n_seq-1.
+ *   ids, token_types (may be NULL): device int64 [Σ n_b]; cap_ids: device int64 [Σ c_b]; vis / aud: device f32
+ *     [n_seq][n_embd] already projected, or both NULL; has_feat: device uint8 [n_seq] or NULL (ergm_embed_packed).  */
+int ergm_decode_admit(ergm_decode_plan* plan, int n_seq, const int* slots, const int* lens, const int* cap_lens,
+                      const int* max_new, const int* meta, const int64_t* ids, const int64_t* token_types,
+                      const int64_t* cap_ids, const float* vis, const float* aud, const uint8_t* has_feat,
+                      void* workspace, size_t ws_bytes, void* stream);
+/* Kernel launches of one ergm_decode_admit of n_seq sequences with `rows` packed token rows and `cap_rows` packed
+ * caption rows, counted by walking the admission's own launch sequence dry.  Host only.                          */
+int ergm_decode_admit_launches(const ergm_decode_plan* plan, int n_seq, int rows, int cap_rows);
+/* One step over all max_batch slots (ergm_decode_step's kernels at B = max_batch, caption bound cap_max), then the
+ * slot length update: a row not finished gets ++lens, ++row_steps, and finished = 1 when lens reaches stop_lens, so
+ * no row can pass the bound recorded at its admission (n_b + max_new <= max_len) whatever the host does.          */
+int ergm_decode_step_slots(ergm_decode_plan* plan, const int64_t* tokens, const int64_t* token_types, void* stream);
+/* For i < n: ergm_topp_sample_rows(logits, row_ids, row_steps, finished) into tokens_out[i] (device int64
+ * [n][max_batch]), then one step on those tokens typed sp2_id, over every slot.  One stream, no events, nothing read
+ * back: the host looks at tokens_out and finished when it chooses.                                                */
+int ergm_decode_run_slots(ergm_decode_plan* plan, int n, float top_p, uint64_t seed, int64_t eos_id, int64_t sp2_id,
+                          int64_t* tokens_out, void* stream);
 
 /* Library information and errors. */
 int ergm_version(void);

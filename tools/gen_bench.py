@@ -17,11 +17,20 @@ caches rotated through enough buffers to exceed the 256 MiB Infinity Cache where
 and divide the same byte count by the mean duration of attn_decode_kernel (plus attn_decode_merge_kernel when the
 automatic split is above 1).
 
+Continuous batching: 256 requests, prompt 64, captions 64, each with its own max_new_tokens from one
+seeded list, min(64, 1 + a geometric variable of mean 16): short on average with a long tail.  tokens/s = the requested
+tokens (the sum of the list) over the whole call, and ``steps_per_token`` = decode steps executed per requested token.
+  bs32/ns32/fs32  what a user does without it: BatchedGenerator.generate in arrival-order batches of 32 with the batch's
+                  largest max_new_tokens, the lists truncated on the host (the baseline), per engine
+  bc32/nc32/fc32  ContinuousGenerator(max_batch=32) on the same requests
+  admit           one admission of n_seq = 1, 4, 8, 32 such prompts: milliseconds on engines "python" and "native" and
+                  the native launch count; and the ragged attention launch against the n_seq ergm_attn_fwd launches it
+                  replaces (causal, 64 rows each, H = 12), microseconds per call in back-to-back windows of 100
 Without --case the tool runs every case in turn, each in a fresh child process under its own timeout, one at a
 time, and stops at the first that fails.  --cases a,b,c runs those cases in that
 order (e.g. b32,n32,f32,b32,n32,f32 to alternate engines on one box).  For the kernel-time split of one engine:
   rocprofv3 --kernel-trace --stats -d OUT -- python tools/gen_bench.py --case f32
-Usage (GPU box): python tools/gen_bench.py [--case kv|b1|b8|b32|n*|f*|attn] [--cases LIST]"""
+Usage (GPU box): python tools/gen_bench.py [--case kv|b1|b8|b32|n*|f*|attn|bs32|bc32|n?32|f?32|admit] [--cases LIST]"""
 import json
 import os
 import statistics
@@ -31,7 +40,9 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 ENGINES = {"b": "python", "n": "native", "f": "fused"}
-CASES = {"kv": 240, **{e + b: 240 for e in ENGINES for b in ("1", "8", "32")}, "attn": 240}  # seconds a child may take
+CASES = {"kv": 240, **{e + b: 240 for e in ENGINES for b in ("1", "8", "32")}, "attn": 240,   # seconds a child may take
+         **{e + m + "32": 300 for e in ENGINES for m in "sc"}, "admit": 240}
+N_REQ, REQ_MEAN = 256, 16
 PROMPT = CAPS = NEW = 64
 TOP_P, NO_EOS, SP2 = 0.95, -1, 50259
 REPEATS = 5
@@ -78,6 +89,94 @@ def _generation(case):
                       "ms_all": [round(x, 2) for x in ms], "tokens_per_s": round(B * NEW / med * 1e3, 1)}), flush=True)
 
 
+def _setup_requests(n):
+    import torch
+    from ergm_amd.config import ERGMConfig, NO_DROPOUT
+    from ergm_amd.model import GPT2LMHeadModel
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = GPT2LMHeadModel(ERGMConfig(**NO_DROPOUT), device=dev)
+    g = torch.Generator().manual_seed(1)
+    prompts = [(torch.randint(0, 50000, (1, PROMPT), generator=g).to(dev), torch.full((1, PROMPT), SP2, device=dev),
+                torch.randint(0, 50000, (1, CAPS), generator=g).to(dev), None, None) for _ in range(n)]
+    geo = torch.distributions.Geometric(probs=torch.tensor(1.0 / REQ_MEAN))   # failures before a success: mean 15
+    torch.manual_seed(2)
+    new = [min(NEW, 2 + int(geo.sample())) for _ in range(n)]                 # 1 + a geometric variable of mean 16
+    return dev, model, prompts, new
+
+
+def _requests(case):
+    from ergm_amd.generate import BatchedGenerator, ContinuousGenerator
+    dev, model, prompts, new = _setup_requests(N_REQ)
+    engine, B = ENGINES[case[0]], int(case[2:])
+    steps, admits = [0], [N_REQ // B]
+    if case[1] == "s":
+        gen = BatchedGenerator(model, max_batch=B, max_len=PROMPT + NEW, engine=engine)
+
+        def run():
+            steps[0] = 0
+            for i in range(0, N_REQ, B):
+                k = max(new[i:i + B])
+                out = gen.generate(prompts[i:i + B], top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2, seed=7, max_new_tokens=k)
+                out = [r[:m] for r, m in zip(out, new[i:i + B])]
+                assert [len(r) for r in out] == new[i:i + B]
+                steps[0] += k - 1
+    else:
+        gen = ContinuousGenerator(model, max_batch=B, max_len=PROMPT + NEW, cap_max=CAPS, engine=engine)
+
+        def run():
+            s0, a0 = gen.sched.steps, gen.admit_calls
+            out = gen.generate(prompts, top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2, seed=7, max_new_tokens=new)
+            assert [len(r) for r in out] == new
+            steps[0], admits[0] = gen.sched.steps - s0, gen.admit_calls - a0
+    run()
+    ms = [_event_ms(run) for _ in range(REPEATS)]
+    med = statistics.median(ms)
+    print(json.dumps({"case": case, "engine": engine, "B": B, "requests": N_REQ, "requested_tokens": sum(new),
+                      "max_new_mean": round(sum(new) / N_REQ, 2), "max_new_max": max(new), "decode_steps": steps[0],
+                      "steps_per_token": round(steps[0] / sum(new), 4),
+                      "admit_calls": admits[0], "ms_median": round(med, 2),
+                      "ms_all": [round(x, 2) for x in ms], "tokens_per_s": round(sum(new) / med * 1e3, 1)}), flush=True)
+
+
+def _admission():
+    import torch
+    from ergm_amd import ops
+    from ergm_amd.generate import ContinuousGenerator
+    dev, model, prompts, _ = _setup_requests(32)
+    H, E, N = 12, 768, 100
+    for n in (1, 4, 8, 32):
+        row = {"case": "admit", "n_seq": n, "rows": n * PROMPT}
+        for engine in ("python", "native"):
+            gen = ContinuousGenerator(model, max_batch=32, max_len=PROMPT + NEW, cap_max=CAPS, engine=engine)
+            run = lambda: gen.admit(list(range(n)), prompts[:n])
+            run()
+            row[f"{engine}_ms"] = round(statistics.median(_event_ms(run) for _ in range(REPEATS)), 3)
+            if engine == "native":
+                row["native_launches"] = gen.admit_launches(n, n * PROMPT, n * CAPS)
+        # one ragged launch against n ergm_attn_fwd launches over the same packed qkv rows
+        qkv = torch.randn(n * PROMPT, 3 * E, device=dev).bfloat16()
+        o = torch.empty(n * PROMPT, E, dtype=torch.bfloat16, device=dev)
+        lse = torch.empty(H * n * PROMPT, dtype=torch.float32, device=dev)
+        st = torch.arange(0, n * PROMPT, PROMPT, dtype=torch.int32, device=dev)
+        ln = torch.full((n,), PROMPT, dtype=torch.int32, device=dev)
+
+        def ragged():
+            for _ in range(N):
+                ops.attn_fwd_ragged(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], st, ln, st, ln, H, PROMPT, PROMPT, True, o=o)
+
+        def per_seq():
+            for _ in range(N):
+                for b in range(n):
+                    r = slice(b * PROMPT, (b + 1) * PROMPT)
+                    ops.attn_fwd(qkv[r, :E], qkv[r, E:2 * E], qkv[r, 2 * E:], 1, H, PROMPT, PROMPT, True, o=o[r],
+                                 lse=lse[:H * PROMPT].view(1, H, PROMPT))
+        for name, fn in (("ragged_us", ragged), ("per_sequence_us", per_seq)):
+            fn()
+            row[name] = round(statistics.median(_event_ms(fn) for _ in range(REPEATS)) / N * 1e3, 2)
+        print(json.dumps(row), flush=True)
+
+
 def _attention():
     import torch
     from ergm_amd import ops
@@ -112,7 +211,14 @@ def main():
         case = sys.argv[sys.argv.index("--case") + 1]
         if case not in CASES:
             raise SystemExit(f"unknown case {case}")
-        _attention() if case == "attn" else _generation(case)
+        if case == "attn":
+            _attention()
+        elif case == "admit":
+            _admission()
+        elif len(case) == 4 and case[1] in "sc":
+            _requests(case)
+        else:
+            _generation(case)
         return
     order = sys.argv[sys.argv.index("--cases") + 1].split(",") if "--cases" in sys.argv else list(CASES)
     for case in order:
