@@ -104,6 +104,7 @@ _SIGS = {
     "ergm_quant_weight_mx": (i32, [vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp]),
     "ergm_attn_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "ergm_attn_fwd_ragged": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp] + [i32] * 11 + [vp]),
+    "ergm_attn_fwd_extend": (i32, [vp, vp, vp, vp, vp, vp, vp, vp] + [i32] * 10 + [vp]),
     "ergm_attn_tune": (i32, [i32]),
     "ergm_attn_decode_workspace_size": (sz, [i32, i32, i32]),
     "ergm_attn_decode": (i32, [vp, i32, vp, vp, i64, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, sz, vp]),
@@ -111,6 +112,7 @@ _SIGS = {
     "ergm_topp_sample": (i32, [vp, i32, i32, i32, f32, C.c_uint64, C.c_uint32, vp, i64, vp, vp, vp, vp]),
     "ergm_topp_sample_rows": (i32, [vp, i32, i32, i32, f32, C.c_uint64, vp, vp, vp, i64, vp, vp, vp, vp]),
     "ergm_rows_to_slots": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp, i64, i64, i32, i32, i32, vp]),
+    "ergm_rows_to_slots_at": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, i64, i64, i32, i32, i32, vp]),
     "ergm_embed_packed": (i32, [vp] * 12 + [i32] * 5 + [vp, vp, i32, i32, i32, i32, vp]),
     "ergm_attn_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp] + [i32] * 13 + [vp, vp, vp]),
     "ergm_linear_rows": (i32, [C.POINTER(LinearRowsDesc), vp, vp, vp, vp]),
@@ -127,6 +129,9 @@ _SIGS = {
     "ergm_decode_admit": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, vp, vp, vp, vp,
                                 vp, vp, vp, sz, vp]),
     "ergm_decode_admit_launches": (i32, [vp, i32, i32, i32]),
+    "ergm_decode_extend": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, vp,
+                                 vp, vp, vp, sz, vp]),
+    "ergm_decode_extend_launches": (i32, [vp, i32, i32]),
     "ergm_decode_step_slots": (i32, [vp, vp, vp, vp]),
     "ergm_decode_run_slots": (i32, [vp, i32, f32, C.c_uint64, i64, i64, vp, vp]),
     "ergm_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
@@ -180,6 +185,7 @@ _SIGS = {
     "ergm_model_stage_wait": (i32, [vp, i32, vp]),
 }
 ADMIT_META_ROWS = 10  # ERGM_ADMIT_META_ROWS
+EXTEND_META_ROWS = 12  # ERGM_EXTEND_META_ROWS
 EXPORTED = sorted(_SIGS)
 
 _lib = None

@@ -20,6 +20,9 @@
 // the fused short kernel instead: one 8-wave workgroup per (b, h) holding every operand in LDS, the whole
 // backward in one launch; it evaluates every product in the same order as the tiled kernels
 // (bit-identical).  The forward is tiled at every length.
+// Inference forwards on the same tile body: packed sequences of different lengths in one launch
+// (attn_fwd_ragged_kernel), and packed new rows over caches that already hold a past, the causal diagonal shifted by
+// the past length (attn_fwd_extend_kernel).
 // Softmax arithmetic in the exp2 domain (v_exp_f32 is 2^x): exp(scale·s − shift) = exp2(fma(s, c, −shift·log2e))
 // with c = scale·log2e, one FMA + one v_exp per score; tiles a wave sees entirely unmasked (uniform
 // test per wave and tile) skip the mask compares.
@@ -576,6 +579,81 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_ragged_kernel(AttnArgs a, Rag
                                 nullptr);
     }
     fwd_store<LSE>(a, 0, h, q, o, m, l);
+}
+
+// Causal forward of packed new query rows over a cache that already holds a past (ergm_attn_fwd_extend): sequence b
+// owns n = q_len[b] packed query rows and Sk = k_len[b] >= n key rows, the last n of which are the new rows' own; query
+// row s sits at absolute position past + s (past = Sk - n) and sees keys 0 .. past + s.  Query tiles are counted in
+// ABSOLUTE positions, tile t = positions 64t .. 64t + 63, and a sequence runs tiles past / 64 .. ceil(Sk / 64) - 1 (at
+// most ceil(n / 64) + 1 of them, the grid's x extent; the last tile, the longest key loop, first).  The workgroup of
+// (sequence, tile, head) then holds the queries, per wave and lane, that attn_fwd_kernel<causal>(B = 1, Sq = Sk) holds
+// for that tile and walks the same key tiles with the same mask decisions, so output row s is bitwise that call's row
+// past + s.  A lane's column of Sᵀ and Oᵀ depends on its own query alone (the row reductions run over the 4 lanes of
+// one query), so the lanes below `past`, which load zeros and store nothing, do not touch the others.  Tiles counted
+// from the chunk's first row would make the early queries of a tile walk one more, fully masked, key tile, whose
+// rescale exp2(fma(m, c, -m·c)) is not exactly 1.
+// Everything read from the metadata arrays is clamped to the packed extents before an address is formed, q_len to k_len.
+template <int NS>
+__global__ __launch_bounds__(256, 4) void attn_fwd_extend_kernel(AttnArgs a, RaggedMeta r) {
+    __shared__ __attribute__((aligned(16))) char ring[NS * 2 * AT_TILE_BYTES];  // [stage][K|V]
+    const int b = blockIdx.z, h = blockIdx.y;
+    const int Sk = max(0, min(r.k_len[b], min(r.max_k, r.total_k)));
+    const int n = max(0, min(r.q_len[b], min(min(r.max_q, r.total_q), Sk)));
+    const int past = Sk - n;
+    const int tlast = (Sk + AT_T - 1) / AT_T - 1;  // tile of the last position
+    const int ntile = n > 0 ? tlast - past / AT_T + 1 : 0;
+    if ((int)blockIdx.x >= ntile) return;  // uniform over the workgroup
+    const int qs = max(0, min(r.q_start[b], r.total_q - n));
+    const int ks = max(0, min(r.k_start[b], r.total_k - Sk));
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int i16 = lane & 15, g = lane >> 4;
+    const int qblk = (tlast - (int)blockIdx.x) * AT_T;
+    const int q = qblk + wave * 16 + i16;  // this lane's query: its absolute position in the sequence
+    const bool mine = q >= past && q < Sk;
+    const size_t qrow = (size_t)qs + (size_t)(mine ? q - past : 0);  // its packed row (the sequence's first for a dead lane)
+    const float c = a.scale * AT_LOG2E;
+    const __bf16* Kb = a.k + (size_t)ks * a.ldk + h * AT_D;
+    const __bf16* Vb = a.v + (size_t)ks * a.ldv + h * AT_D;
+
+    bf16x8 qf[2];
+    {
+        const __bf16* Qr = a.q + qrow * a.ldq + h * AT_D;
+        qf[0] = load_frag_global(Qr, 0, 0, mine ? 1 : 0, 8 * g);
+        qf[1] = load_frag_global(Qr, 0, 0, mine ? 1 : 0, 32 + 8 * g);
+    }
+    vm_ready(qf[0]);
+    vm_ready(qf[1]);
+
+    f32x4 o[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+
+    const int qlast = min(Sk, qblk + AT_T) - 1;
+    const int nkt = min((Sk + AT_T - 1) / AT_T, qlast / AT_T + 1);
+    auto issue = [&](int kt) {
+        char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
+        AttnTile::issue(st, Kb, a.ldk, kt * AT_T, Sk, 0, wave);
+        AttnTile::issue(st + AT_TILE_BYTES, Vb, a.ldv, kt * AT_T, Sk, 0, wave);
+    };
+    for (int s = 0; s < NS - 1 && s < nkt; ++s) issue(s);
+    for (int kt = 0; kt < nkt; ++kt) {
+        ring_sync<4, NS>(min(NS - 2, nkt - 1 - kt));
+        if (kt + NS - 1 < nkt) issue(kt + NS - 1);
+        const char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
+        fwd_tile<true, false>(st, st + AT_TILE_BYTES, kt * AT_T, q, qblk + wave * 16, Sk, c, qf, o, m, l, a.drop, 0, nullptr);
+    }
+    if (!mine) return;
+    // fwd_store's row, at the packed row
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    __bf16* Ob = a.out + qrow * a.ldo + h * AT_D;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        bf16x4 w;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) w[rr] = f2bf(o[d][rr] * inv);
+        *reinterpret_cast<bf16x4*>(Ob + d * 16 + 4 * g) = w;
+    }
 }
 
 // Cross-attention forward with the query projection inside (non-causal): the workgroup of (query block, h, b)
@@ -1288,6 +1366,31 @@ extern "C" int ergm_attn_fwd_ragged(const void* q, const void* k, const void* v,
         else ERGM_LAUNCH((attn_fwd_ragged_kernel<false, 2, false>), grid, dim3(256), 0, s, a, r);
     }
     return check_launch("attn_fwd_ragged");
+}
+
+extern "C" int ergm_attn_fwd_extend(const void* q, const void* k, const void* v, void* o, const int* q_start, const int* q_len,
+                                    const int* k_start, const int* k_len, int n_seq, int H, int total_q, int total_k,
+                                    int max_q, int max_k, int ldq, int ldk, int ldv, int ldo, void* stream) {
+    ERGM_CHECK_ARG(q && k && v && o && q_start && q_len && k_start && k_len, "attn_fwd_extend: null argument");
+    ERGM_CHECK_ARG(n_seq > 0 && n_seq <= 65535 && H > 0 && H <= 65535, "attn_fwd_extend: bad shape n_seq %d H %d", n_seq, H);
+    ERGM_CHECK_ARG(total_q > 0 && total_k > 0 && max_q > 0 && max_q <= total_q && max_k > 0 && max_k <= total_k,
+                   "attn_fwd_extend: bad extents total_q %d total_k %d max_q %d max_k %d", total_q, total_k, max_q, max_k);
+    ERGM_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0,
+                   "attn_fwd_extend: leading dims must be multiples of 8 (output: 4)");
+    ERGM_CHECK_ARG(ldq >= H * AT_D && ldk >= H * AT_D && ldv >= H * AT_D && ldo >= H * AT_D,
+                   "attn_fwd_extend: leading dim < H*64");
+    ERGM_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v), "attn_fwd_extend: pointers must be 16-byte aligned");
+    AttnArgs a{};
+    a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v;
+    a.out = (__bf16*)o;
+    a.B = 1; a.H = H;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.scale = 0.125f;
+    const RaggedMeta r{q_start, q_len, k_start, k_len, total_q, total_k, max_q, max_k};
+    // max_q new rows starting anywhere inside a tile of absolute positions touch at most ceil(max_q / 64) + 1 tiles
+    const dim3 grid(cdiv(max_q, AT_T) + 1, H, n_seq);
+    ERGM_LAUNCH((attn_fwd_extend_kernel<2>), grid, dim3(256), 0, as_stream(stream), a, r);
+    return check_launch("attn_fwd_extend");
 }
 
 extern "C" int ergm_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,

@@ -390,19 +390,22 @@ __global__ void fill_i64_kernel(int64_t* __restrict__ p, int64_t v, int n) {
 // Row t of sequence b (packed row start[b] + t of src) goes to dst + slot[b]·ld_slot + t·ld_row; strides and
 // row_bytes in bytes, 16-byte copies, one wave per row.  Everything read from the device arrays is checked before an
 // address is formed: the length is clamped to [0, min(max_rows, slot_rows)], the start to the packed extent, and a
-// sequence whose slot lies outside [0, n_slots) writes nothing.
+// sequence whose slot lies outside [0, n_slots) writes nothing.  dst_row0 (ergm_rows_to_slots_at; nullptr: 0): row t
+// lands in slot row dst_row0[b] + t, the first row clamped to [0, slot_rows] and the length to the rows left after it.
 __global__ __launch_bounds__(256) void rows_to_slots_kernel(const char* __restrict__ src, int64_t ld_src,
                                                             const int* __restrict__ start, const int* __restrict__ len,
                                                             const int* __restrict__ slot, int total_rows, int max_rows,
                                                             char* __restrict__ dst, int64_t ld_slot, int64_t ld_row,
-                                                            int row_bytes, int n_slots, int slot_rows) {
+                                                            int row_bytes, int n_slots, int slot_rows,
+                                                            const int* __restrict__ dst_row0) {
     const int b = blockIdx.y, t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int n = max(0, min(len[b], min(min(max_rows, slot_rows), total_rows)));
+    const int d0 = dst_row0 ? max(0, min(dst_row0[b], slot_rows)) : 0;
+    const int n = max(0, min(len[b], min(min(max_rows, slot_rows - d0), total_rows)));
     const int sl = slot[b];
     if (t >= n || sl < 0 || sl >= n_slots) return;
     const int r0 = max(0, min(start[b], total_rows - n));
     const char* s = src + (int64_t)(r0 + t) * ld_src;
-    char* d = dst + (int64_t)sl * ld_slot + (int64_t)t * ld_row;
+    char* d = dst + (int64_t)sl * ld_slot + (int64_t)(d0 + t) * ld_row;
     for (int c = lane * 16; c < row_bytes; c += 64 * 16)
         *reinterpret_cast<uint4*>(d + c) = *reinterpret_cast<const uint4*>(s + c);
 }
@@ -426,6 +429,22 @@ __global__ void slots_admit_kernel(const int* __restrict__ slot, const int* __re
     finished[sl] = 0;
 }
 
+// The state of the slots an extension continued: the new length and bound, live again.  cap_lens, row_ids and
+// row_steps stay: the captions are the admission's, and the request goes on drawing from fresh counters.
+__global__ void slots_extend_kernel(const int* __restrict__ slot, const int* __restrict__ past, const int* __restrict__ n_new,
+                                    const int* __restrict__ max_new, int n_seq, int n_slots, int max_len,
+                                    int* __restrict__ lens, int* __restrict__ stop_lens, uint8_t* __restrict__ finished) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_seq) return;
+    const int sl = slot[b];
+    if (sl < 0 || sl >= n_slots) return;
+    const int p = max(0, min(past[b], max_len));
+    const int n = p + max(0, min(n_new[b], max_len - p));
+    lens[sl] = n;
+    stop_lens[sl] = max(n, min(n + max(max_new[b], 0), max_len));
+    finished[sl] = 0;
+}
+
 // The length update of a step over every slot: a live row advances by the token just appended and its draw counter
 // with it, and finishes when it reaches the bound recorded at its admission, so no row passes its bound whatever the
 // host does between two looks.
@@ -445,6 +464,12 @@ int decode_slots_admit(const int* slot, const int* n_tok, const int* n_cap, cons
     ERGM_LAUNCH(slots_admit_kernel, dim3(cdiv(n_seq, 256)), dim3(256), 0, s, slot, n_tok, n_cap, max_new, req, n_seq, n_slots,
                 max_len, cap_max, lens, cap_lens, stop_lens, row_ids, row_steps, finished);
     return check_launch("decode_slots_admit");
+}
+int decode_slots_extend(const int* slot, const int* past, const int* n_new, const int* max_new, int n_seq, int n_slots,
+                        int max_len, int* lens, int* stop_lens, uint8_t* finished, hipStream_t s) {
+    ERGM_LAUNCH(slots_extend_kernel, dim3(cdiv(n_seq, 256)), dim3(256), 0, s, slot, past, n_new, max_new, n_seq, n_slots, max_len,
+                lens, stop_lens, finished);
+    return check_launch("decode_slots_extend");
 }
 int decode_slots_advance(int* lens, uint32_t* row_steps, uint8_t* finished, const int* stop_lens, int B, hipStream_t s) {
     ERGM_LAUNCH(slots_advance_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, lens, row_steps, finished, stop_lens, B);
@@ -550,21 +575,38 @@ extern "C" int ergm_topp_sample_rows(const float* logits, int ldl, int B, int V,
                        kept, kept_mass, stream);
 }
 
+namespace {
+int rows_to_slots_launch(const char* what, const void* src, int64_t ld_src, const int* start, const int* len, const int* slot,
+                                  int n_seq, int total_rows, int max_rows, void* dst, int64_t ld_slot, int64_t ld_row,
+                                  int row_bytes, int n_slots, int slot_rows, const int* dst_row0, void* stream) {
+    ERGM_CHECK_ARG(src && start && len && slot && dst, "%s: null argument", what);
+    ERGM_CHECK_ARG(n_seq > 0 && n_seq <= 65535 && total_rows > 0 && max_rows > 0 && max_rows <= total_rows && n_slots > 0 &&
+                       slot_rows > 0,
+                   "%s: bad shape n_seq %d total_rows %d max_rows %d n_slots %d slot_rows %d", what, n_seq, total_rows,
+                   max_rows, n_slots, slot_rows);
+    ERGM_CHECK_ARG(row_bytes > 0 && row_bytes % 16 == 0 && ld_src % 16 == 0 && ld_slot % 16 == 0 && ld_row % 16 == 0,
+                   "%s: row_bytes and the strides (bytes) must be multiples of 16", what);
+    ERGM_CHECK_ARG(ld_src >= row_bytes && ld_row >= row_bytes && ld_slot >= (int64_t)(slot_rows - 1) * ld_row + row_bytes,
+                   "%s: stride shorter than the rows it spans", what);
+    ERGM_CHECK_ARG(aligned16(src) && aligned16(dst), "%s: 16-byte alignment", what);
+    ERGM_LAUNCH(rows_to_slots_kernel, dim3(cdiv(std::min(max_rows, slot_rows), 4), n_seq), dim3(256), 0, as_stream(stream),
+                reinterpret_cast<const char*>(src), ld_src, start, len, slot, total_rows, max_rows,
+                reinterpret_cast<char*>(dst), ld_slot, ld_row, row_bytes, n_slots, slot_rows, dst_row0);
+    return check_launch(what);
+}
+}  // namespace
+
 extern "C" int ergm_rows_to_slots(const void* src, int64_t ld_src, const int* start, const int* len, const int* slot,
                                   int n_seq, int total_rows, int max_rows, void* dst, int64_t ld_slot, int64_t ld_row,
                                   int row_bytes, int n_slots, int slot_rows, void* stream) {
-    ERGM_CHECK_ARG(src && start && len && slot && dst, "rows_to_slots: null argument");
-    ERGM_CHECK_ARG(n_seq > 0 && n_seq <= 65535 && total_rows > 0 && max_rows > 0 && max_rows <= total_rows && n_slots > 0 &&
-                       slot_rows > 0,
-                   "rows_to_slots: bad shape n_seq %d total_rows %d max_rows %d n_slots %d slot_rows %d", n_seq, total_rows,
-                   max_rows, n_slots, slot_rows);
-    ERGM_CHECK_ARG(row_bytes > 0 && row_bytes % 16 == 0 && ld_src % 16 == 0 && ld_slot % 16 == 0 && ld_row % 16 == 0,
-                   "rows_to_slots: row_bytes and the strides (bytes) must be multiples of 16");
-    ERGM_CHECK_ARG(ld_src >= row_bytes && ld_row >= row_bytes && ld_slot >= (int64_t)(slot_rows - 1) * ld_row + row_bytes,
-                   "rows_to_slots: stride shorter than the rows it spans");
-    ERGM_CHECK_ARG(aligned16(src) && aligned16(dst), "rows_to_slots: 16-byte alignment");
-    ERGM_LAUNCH(rows_to_slots_kernel, dim3(cdiv(std::min(max_rows, slot_rows), 4), n_seq), dim3(256), 0, as_stream(stream),
-                reinterpret_cast<const char*>(src), ld_src, start, len, slot, total_rows, max_rows,
-                reinterpret_cast<char*>(dst), ld_slot, ld_row, row_bytes, n_slots, slot_rows);
-    return check_launch("rows_to_slots");
+    return rows_to_slots_launch("rows_to_slots", src, ld_src, start, len, slot, n_seq, total_rows, max_rows, dst, ld_slot, ld_row,
+                                row_bytes, n_slots, slot_rows, nullptr, stream);
+}
+
+extern "C" int ergm_rows_to_slots_at(const void* src, int64_t ld_src, const int* start, const int* len, const int* slot,
+                                     const int* dst_row0, int n_seq, int total_rows, int max_rows, void* dst, int64_t ld_slot,
+                                     int64_t ld_row, int row_bytes, int n_slots, int slot_rows, void* stream) {
+    ERGM_CHECK_ARG(dst_row0, "rows_to_slots_at: null dst_row0");
+    return rows_to_slots_launch("rows_to_slots_at", src, ld_src, start, len, slot, n_seq, total_rows, max_rows, dst, ld_slot,
+                                ld_row, row_bytes, n_slots, slot_rows, dst_row0, stream);
 }

@@ -7,8 +7,9 @@
 // place of each LayerNorm + GEMM pair and each plain GEMM of the blocks.
 //
 // Slot mode (ergm_decode_bind_slots) serves ContinuousGenerator: the same step over all max_batch cache slots with the
-// slot length update at its end, and the admission of new sequences into free slots (walk_admit: the prefill over
-// packed ragged rows, written once like the step so that ergm_decode_admit_launches counts what runs).
+// slot length update at its end, the admission of new sequences into free slots (walk_admit: the prefill over
+// packed ragged rows, written once like the step so that ergm_decode_admit_launches counts what runs), and the
+// extension of occupied slots by more than one token (walk_extend: packed new rows over the slots' own caches).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +28,8 @@ int decode_slots_admit(const int* slot, const int* n_tok, const int* n_cap, cons
                        int n_slots, int max_len, int cap_max, int* lens, int* cap_lens, int* stop_lens, uint32_t* row_ids,
                        uint32_t* row_steps, uint8_t* finished, hipStream_t s);
 int decode_slots_advance(int* lens, uint32_t* row_steps, uint8_t* finished, const int* stop_lens, int B, hipStream_t s);
+int decode_slots_extend(const int* slot, const int* past, const int* n_new, const int* max_new, int n_seq, int n_slots,
+                        int max_len, int* lens, int* stop_lens, uint8_t* finished, hipStream_t s);
 }  // namespace ergm
 
 using namespace ergm;
@@ -414,6 +417,73 @@ int walk_admit(const ergm_decode_plan* P, Walk& w, const Admit& a) {
     return ERGM_OK;
 }
 
+// ---- slot mode: the extension (ergm_decode_extend) -----------------------------------------------------------
+// What one extension was called with; it runs on the admission's workspace (one caption row carved, none used).
+struct Extend {
+    int n_seq, R, max_n, max_k, max_c;  // sequences, packed new rows, the longest chunk, past + chunk and caption
+    const int* meta;                    // device [ERGM_EXTEND_META_ROWS][n_seq]
+    const int64_t *ids, *tt;
+    const int* pos;                     // device [R]: the position of every packed row
+    Admit a;                            // the workspace, for admit_ln / admit_gemm
+    const int* row(int i) const { return meta ? meta + (size_t)i * n_seq : nullptr; }
+};
+
+// The extension's launch sequence, written once: a dry walk (w.dry) only counts.
+int walk_extend(const ergm_decode_plan* P, Walk& w, const Extend& x) {
+    const ergm_decode_dims& d = P->d;
+    const int E = d.n_embd, F = d.n_inner, H = d.n_head, R = x.R, n = x.n_seq;
+    const Admit& a = x.a;
+    const AdmitWs& W = a.ws;
+    const int *slot = x.row(0), *q0 = x.row(1), *qn = x.row(2), *past = x.row(3), *k0 = x.row(4), *kn = x.row(5), *c0 = x.row(6),
+              *cn = x.row(7), *last = x.row(9), *ones = x.row(10), *iota = x.row(11);
+    const int64_t kv_row = (int64_t)2 * E * 2;  // bytes of a K | V row
+    if (w.on())
+        ERGM_TRY(ergm_embed_rows(x.ids, x.tt, x.pos, P->p.wte, P->p.wpe, W.h, R, E, d.vocab_pad, d.n_positions, w.s));
+    for (int l = 0; l < d.n_layer; ++l) {
+        const __bf16* kv = w.dry ? nullptr : reinterpret_cast<const __bf16*>(P->kv[l]);
+        const __bf16* xkv = w.dry ? nullptr : reinterpret_cast<const __bf16*>(P->xkv[l]);
+        ERGM_TRY(admit_ln(P, w, a, W.h, R, lf(P, l, ERGM_T_LN1_W), lf(P, l, ERGM_T_LN1_W + 1)));
+        ERGM_TRY(admit_gemm(w, a, R, 3 * E, E, W.x, lb(P, l, ERGM_T_ATTN_W), ERGM_KN, W.qkv, ERGM_BF16, ERGM_EPI_BIAS,
+                            lf(P, l, ERGM_T_ATTN_W + 1), nullptr, nullptr));
+        // the new rows' K | V into rows past_b .. of their slots, then the queries over the whole slot
+        if (w.on())
+            ERGM_TRY(ergm_rows_to_slots_at(W.qkv + E, (int64_t)3 * E * 2, q0, qn, slot, past, n, R, x.max_n, P->kv[l],
+                                           (int64_t)d.max_len * kv_row, kv_row, (int)kv_row, d.max_batch, d.max_len, w.s));
+        if (w.on())
+            ERGM_TRY(ergm_attn_fwd_extend(W.qkv, kv, kv + E, W.att, q0, qn, k0, kn, n, H, R, d.max_batch * d.max_len, x.max_n,
+                                          x.max_k, 3 * E, 2 * E, 2 * E, E, w.s));
+        ERGM_TRY(admit_gemm(w, a, R, E, E, W.att, lb(P, l, ERGM_T_APROJ_W), ERGM_KN, W.h, ERGM_F32, ERGM_EPI_BIAS_RESID,
+                            lf(P, l, ERGM_T_APROJ_W + 1), W.h, nullptr));
+        ERGM_TRY(admit_ln(P, w, a, W.h, R, lf(P, l, ERGM_T_LNX_W), lf(P, l, ERGM_T_LNX_W + 1)));
+        ERGM_TRY(admit_gemm(w, a, R, E, E, W.x, lb(P, l, ERGM_T_XQ_W), ERGM_KN, W.q, ERGM_BF16, ERGM_EPI_BIAS,
+                            lf(P, l, ERGM_T_XQ_W + 1), nullptr, nullptr));
+        // the caption rows the admission left in the slot: xkv[l] as packed rows, sequence b's at slot_b · cap_max
+        if (w.on())
+            ERGM_TRY(ergm_attn_fwd_ragged(W.q, xkv, xkv + E, W.att, nullptr, q0, qn, c0, cn, n, H, R, d.max_batch * d.cap_max,
+                                          x.max_n, x.max_c, E, 2 * E, 2 * E, E, 0, w.s));
+        ERGM_TRY(admit_gemm(w, a, R, E, E, W.att, lb(P, l, ERGM_T_XPROJ_W), ERGM_KN, W.h, ERGM_F32, ERGM_EPI_BIAS_RESID,
+                            lf(P, l, ERGM_T_XPROJ_W + 1), W.h, nullptr));
+        ERGM_TRY(admit_ln(P, w, a, W.h, R, lf(P, l, ERGM_T_LN2_W), lf(P, l, ERGM_T_LN2_W + 1)));
+        ERGM_TRY(admit_gemm(w, a, R, F, E, W.x, lb(P, l, ERGM_T_FC_W), ERGM_KN, W.act, ERGM_BF16, ERGM_EPI_BIAS_GELU,
+                            lf(P, l, ERGM_T_FC_W + 1), nullptr, W.pre));
+        ERGM_TRY(admit_gemm(w, a, R, E, F, W.act, lb(P, l, ERGM_T_MPROJ_W), ERGM_KN, W.h, ERGM_F32, ERGM_EPI_BIAS_RESID,
+                            lf(P, l, ERGM_T_MPROJ_W + 1), W.h, nullptr));
+    }
+    // the last new row of every sequence -> ln_f -> the head -> logits[slot]
+    if (w.on())
+        ERGM_TRY(ergm_rows_to_slots(W.h, (int64_t)E * 4, last, ones, iota, n, R, 1, W.hl, (int64_t)E * 4, (int64_t)E * 4, E * 4, n,
+                                    1, w.s));
+    ERGM_TRY(admit_ln(P, w, a, W.hl, n, P->p.ln_f_w, P->p.ln_f_b));
+    ERGM_TRY(admit_gemm(w, a, n, d.vocab_pad, E, W.x, P->p.wte_b, ERGM_NK, W.lg, ERGM_F32, ERGM_EPI_NONE, nullptr, nullptr,
+                        nullptr));
+    if (w.on())
+        ERGM_TRY(ergm_rows_to_slots(W.lg, (int64_t)d.vocab_pad * 4, iota, ones, slot, n, n, 1, P->logits, (int64_t)d.vocab_pad * 4,
+                                    (int64_t)d.vocab_pad * 4, d.vocab_pad * 4, d.max_batch, 1, w.s));
+    if (w.on())
+        ERGM_TRY(decode_slots_extend(slot, past, qn, x.row(8), n, d.max_batch, d.max_len, P->lens, P->stop_lens, P->finished, w.s));
+    return ERGM_OK;
+}
+
 int slots_ready(const ergm_decode_plan* P, const char* what) {
     ERGM_CHECK_ARG(P, "%s: null plan", what);
     ERGM_CHECK_ARG(P->slots, "%s: no slots bound (ergm_decode_bind_slots)", what);
@@ -609,6 +679,59 @@ extern "C" int ergm_decode_admit_launches(const ergm_decode_plan* P, int n_seq, 
     admit_carve(P->d, rows, cap_rows, n_seq, &a.ws, reinterpret_cast<char*>(P->h));
     Walk w{true};
     ERGM_TRY(walk_admit(P, w, a));
+    return w.count;
+}
+
+extern "C" int ergm_decode_extend(ergm_decode_plan* P, int n_seq, const int* slots, const int* past, const int* lens,
+                                  const int* cap_lens, const int* max_new, const int* meta, const int64_t* ids,
+                                  const int64_t* token_types, const int* pos, void* workspace, size_t ws_bytes, void* stream) {
+    ERGM_TRY(slots_ready(P, "decode_extend"));
+    const ergm_decode_dims& d = P->d;
+    ERGM_CHECK_ARG(slots && past && lens && cap_lens && max_new && meta && ids && pos && workspace, "decode_extend: null argument");
+    ERGM_CHECK_ARG(n_seq >= 1 && n_seq <= d.max_batch, "decode_extend: n_seq %d outside [1, max_batch %d]", n_seq, d.max_batch);
+    Extend x{};
+    std::vector<char> seen(d.max_batch, 0);
+    int64_t R = 0;
+    for (int b = 0; b < n_seq; ++b) {
+        ERGM_CHECK_ARG(slots[b] >= 0 && slots[b] < d.max_batch, "decode_extend: slot %d of sequence %d outside [0, max_batch %d)",
+                       slots[b], b, d.max_batch);
+        ERGM_CHECK_ARG(!seen[slots[b]], "decode_extend: slot %d named twice", slots[b]);
+        seen[slots[b]] = 1;
+        ERGM_CHECK_ARG(lens[b] >= 1, "decode_extend: sequence %d gets no new token (n_b %d < 1)", b, lens[b]);
+        ERGM_CHECK_ARG(past[b] >= 2, "decode_extend: sequence %d has a past of %d rows < 2 (positions 0 and 1 belong to the "
+                       "admission)", b, past[b]);
+        ERGM_CHECK_ARG(cap_lens[b] >= 1 && cap_lens[b] <= d.cap_max, "decode_extend: caption of sequence %d has %d rows outside "
+                       "[1, cap_max %d]", b, cap_lens[b], d.cap_max);
+        ERGM_CHECK_ARG(max_new[b] >= 1, "decode_extend: max_new %d of sequence %d < 1", max_new[b], b);
+        ERGM_CHECK_ARG(past[b] <= d.max_len && lens[b] <= d.max_len - past[b] && max_new[b] <= d.max_len - past[b] - lens[b],
+                       "decode_extend: sequence %d: past %d + n_b %d + max_new %d > max_len %d", b, past[b], lens[b], max_new[b],
+                       d.max_len);
+        R += lens[b];
+        x.max_n = std::max(x.max_n, lens[b]), x.max_k = std::max(x.max_k, past[b] + lens[b]);
+        x.max_c = std::max(x.max_c, cap_lens[b]);
+    }
+    ERGM_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "decode_extend: workspace must be 256-byte aligned");
+    ERGM_CHECK_ARG(admit_rows_ok(d, (int)R, 1), "decode_extend: bad row count");
+    const size_t need = admit_carve(d, (int)R, 1, n_seq, &x.a.ws, nullptr);  // this extension alone
+    ERGM_CHECK_ARG(ws_bytes >= need, "decode_extend: %lld packed rows need a workspace of %zu bytes, %zu given", (long long)R, need,
+                   ws_bytes);
+    x.n_seq = n_seq, x.R = (int)R;
+    x.meta = meta, x.ids = ids, x.tt = token_types, x.pos = pos;
+    admit_carve(d, x.R, 1, n_seq, &x.a.ws, reinterpret_cast<char*>(workspace));
+    Walk w{false};
+    w.s = as_stream(stream);
+    return walk_extend(P, w, x);
+}
+
+extern "C" int ergm_decode_extend_launches(const ergm_decode_plan* P, int n_seq, int rows) {
+    ERGM_CHECK_ARG(P && n_seq >= 1 && n_seq <= P->d.max_batch && rows >= n_seq && admit_rows_ok(P->d, rows, 1),
+                   "decode_extend_launches: bad plan or counts (n_seq %d rows %d)", n_seq, rows);
+    Extend x{};
+    x.n_seq = n_seq, x.R = rows, x.max_n = rows, x.max_k = P->d.max_len, x.max_c = P->d.cap_max;
+    // buffer addresses for the GEMM descriptors the walk plans (the plan's own workspace; nothing is launched)
+    admit_carve(P->d, rows, 1, n_seq, &x.a.ws, reinterpret_cast<char*>(P->h));
+    Walk w{true};
+    ERGM_TRY(walk_extend(P, w, x));
     return w.count;
 }
 

@@ -429,12 +429,14 @@ NO_REQUEST = -1
 
 
 class _Request:
-    __slots__ = ("id", "n", "c", "max_new", "payload", "tokens", "slot")
+    __slots__ = ("id", "n", "c", "max_new", "payload", "tokens", "slot", "keep", "past")
 
-    def __init__(self, rid: int, n: int, c: int, max_new: int, payload):
+    def __init__(self, rid: int, n: int, c: int, max_new: int, payload, keep: bool = False, past: int = 0):
         self.id, self.n, self.c, self.max_new, self.payload = rid, n, c, max_new, payload
         self.tokens: List[int] = []
         self.slot = NO_REQUEST
+        self.keep = keep      # park the slot when the request ends
+        self.past = past      # a continuation: the rows its slot already holds (n counts the new ones)
 
 
 class SlotScheduler:
@@ -444,14 +446,26 @@ class SlotScheduler:
       ``.payload``) into the named free slots;
     * ``backend.run_chunk(n)`` runs n sample + step rounds over every slot and returns ``(tokens, finished)``:
       tokens as n lists of one token per slot, finished as one flag per slot, read back once;
-    * ``backend.retire(slot, request)`` (optional) is told when a request leaves its slot.
+    * ``backend.retire(slot, request)`` (optional) is told when a request leaves its slot or is parked in it;
+    * ``backend.extend_requests(slots, requests)`` (optional; needed by ``extend``) appends the ``.n`` new tokens of
+      each continuation (``.payload``) behind the ``.past`` rows its slot holds.
 
     Requests wait in arrival order (FIFO) and are admitted at a look, at most ``max_admit`` sequences and
     ``max_admit_tokens`` packed prompt rows per ``admit`` call, as many calls as fill the free slots; a request that does
     not fit the current call waits for the next one, and nothing overtakes it.  A free slot is chosen by least recent
     admission (ties by index), so the slots take turns.  The host looks once in ``look`` steps (8, the cadence of
     ``BatchedGenerator.generate``): it appends the chunk's tokens to the live requests, each list ending at its first
-    eos (included) or at ``max_new_tokens``, and retires the requests that ended."""
+    eos (included) or at ``max_new_tokens``, and retires the requests that ended.
+
+    Sessions: a request submitted with ``keep=True`` keeps its slot when it ends; it is *parked*, with the length its
+    cache holds: ``n + len(tokens)``, less one when the last token is the eos, because an eos that was drawn is never
+    stepped into the cache, while a request that ends at its bound has its last token there.  (A continuation that
+    wants the eos as a separator begins with it.)  ``extend`` queues more tokens for a parked request; at a look the
+    waiting continuations go first, grouped under the same ``max_admit`` / ``max_admit_tokens`` limits, one
+    ``extend_requests`` call per group, and the admissions into free slots follow.  The new turn's tokens are returned
+    under the same id.  ``release`` frees a parked slot.  A parked slot is stepped like any finished slot: the step's
+    append lands in the row behind its length, which the next extension overwrites before it reads it.  A slot parked
+    with its cache full (length ``max_len``) has no room and cannot be continued, only released."""
 
     def __init__(self, backend, max_batch: int, max_len: int, cap_max: int, max_admit: Optional[int] = None,
                  max_admit_tokens: Optional[int] = None, look: int = 8):
@@ -463,18 +477,23 @@ class SlotScheduler:
         if not 1 <= self.max_admit <= max_batch or self.max_admit_tokens < 1:
             raise ValueError("max_admit must lie in [1, max_batch] and max_admit_tokens be at least 1")
         self.queue: List[_Request] = []
+        self.continuations: List[_Request] = []   # extensions waiting for the next look, in arrival order
         self.live: List[Optional[_Request]] = [None] * max_batch
+        self.parked: dict = {}                # id -> (slot, rows in its cache, caption rows)
+        self._held = set()                    # slots parked or waiting for their continuation: not free
         self._last_admit = [-1] * max_batch   # the admit call that last filled each slot
         self._calls = 0
         self._next_id = 0
-        self._active = set()                  # ids queued or live: a result is returned under its id
+        self._active = set()                  # ids queued, live or parked: a result is returned under its id
         self.steps = 0                        # decode steps run so far
         self.admissions: List[List[tuple]] = []   # per admit call: (request id, slot) pairs, for tests and tools
+        self.extensions: List[List[tuple]] = []   # per extend_requests call: (request id, slot) pairs
 
     def submit(self, n: int, c: int, max_new_tokens: Optional[int] = None, request_id: Optional[int] = None,
-               payload=None) -> int:
+               payload=None, keep: bool = False) -> int:
         """Queue a request with a prompt of n tokens and c caption tokens; returns its id (uint32, arrival order by
-        default).  Raises ValueError when it can never be served: it would not fit a cache or one admission."""
+        default).  ``keep``: park the slot when the request ends, for ``extend``.  Raises ValueError when it can never
+        be served: it would not fit a cache or one admission."""
         if n < 1 or c < 1:
             raise ValueError("empty prompt or caption")
         if n >= self.max_len:
@@ -494,12 +513,65 @@ class SlotScheduler:
             raise ValueError(f"request id {rid} is already queued or running")
         self._active.add(rid)
         self._next_id = (rid + 1) % 2 ** 32 if request_id is None else self._next_id
-        self.queue.append(_Request(rid, n, c, max_new_tokens, payload))
+        self.queue.append(_Request(rid, n, c, max_new_tokens, payload, keep))
         return rid
+
+    def extend(self, request_id: int, n_new: int, max_new_tokens: Optional[int] = None, payload=None,
+               keep: bool = True) -> int:
+        """Queue n_new more tokens (``payload``) for a parked request and up to max_new_tokens new ones behind them
+        (default: to the end of the cache); its slot stays held until the next look.  Raises ValueError when the id is
+        not parked, n_new is outside [1, max_admit_tokens], or the cache has no room for the new rows and one new
+        token; also when the slot holds fewer than 2 rows (a one-token prompt that drew eos at once: the first two
+        positions belong to the admission)."""
+        if request_id not in self.parked:
+            raise ValueError(f"request id {request_id} is not parked")
+        if getattr(self.backend, "extend_requests", None) is None:
+            raise ValueError("the backend cannot extend a request (no extend_requests)")
+        slot, length, c = self.parked[request_id]
+        if not 1 <= n_new <= self.max_admit_tokens:
+            raise ValueError(f"{n_new} new tokens outside [1, max_admit_tokens {self.max_admit_tokens}]")
+        room = self.max_len - length - n_new
+        if room < 1:
+            raise ValueError(f"{length} rows + {n_new} new tokens leave no room for one more in a cache of max_len "
+                             f"{self.max_len}")
+        if length < 2:
+            raise ValueError(f"request id {request_id} holds {length} row: nothing to continue")
+        if max_new_tokens is None:
+            max_new_tokens = room
+        if not 1 <= max_new_tokens <= room:
+            raise ValueError(f"max_new_tokens {max_new_tokens} outside [1, {room}]")
+        del self.parked[request_id]
+        r = _Request(request_id, n_new, c, max_new_tokens, payload, keep, past=length)
+        r.slot = slot
+        self.continuations.append(r)
+        return request_id
+
+    def release(self, request_id: int) -> None:
+        """Free the slot of a parked request."""
+        if request_id not in self.parked:
+            raise ValueError(f"request id {request_id} is not parked")
+        slot, _, _ = self.parked.pop(request_id)
+        self._held.discard(slot)
+        self._active.discard(request_id)
+
+    def _extend(self) -> None:
+        while self.continuations:
+            batch, rows = [], 0
+            while (self.continuations and len(batch) < self.max_admit
+                   and rows + self.continuations[0].n <= self.max_admit_tokens):
+                r = self.continuations.pop(0)
+                rows += r.n
+                batch.append(r)
+            slots = [r.slot for r in batch]
+            self.backend.extend_requests(slots, batch)
+            for r in batch:
+                self._held.discard(r.slot)
+                self.live[r.slot] = r
+            self.extensions.append([(r.id, r.slot) for r in batch])
 
     def _admit(self) -> None:
         while self.queue:
-            free = sorted((s for s in range(self.max_batch) if self.live[s] is None),
+            free = sorted((s for s in range(self.max_batch) if self.live[s] is None and s not in self._held),
                           key=lambda s: (self._last_admit[s], s))
             batch, rows = [], 0
             while (self.queue and len(batch) < min(self.max_admit, len(free))
@@ -517,9 +589,14 @@ class SlotScheduler:
             self._calls += 1
 
     def drain(self, eos_id: int):
-        """Run until the queue and the slots are empty, yielding (id, tokens) of each request as it retires."""
-        while self.queue or any(r is not None for r in self.live):
+        """Run until nothing is queued and nothing is running, yielding (id, tokens) of each request as it retires or
+        is parked; parked sessions do not keep it alive.  Raises RuntimeError when new requests wait, nothing runs and
+        every slot is parked: nothing could ever change."""
+        while self.queue or self.continuations or any(r is not None for r in self.live):
+            self._extend()
             self._admit()
+            if all(r is None for r in self.live):
+                raise RuntimeError(f"{len(self.queue)} request(s) wait and every slot is parked: release a session")
             tokens, finished = self.backend.run_chunk(self.look)
             self.steps += self.look
             for s, r in enumerate(self.live):
@@ -536,7 +613,12 @@ class SlotScheduler:
                     raise RuntimeError(f"slot {s}: the device says finished = {int(finished[s])}, the tokens say {done}")
                 if done:
                     self.live[s] = None
-                    self._active.discard(r.id)
+                    if r.keep:   # an eos that was drawn is never stepped into the cache
+                        rows = r.past + r.n + len(r.tokens) - (1 if r.tokens[-1] == eos_id else 0)
+                        self.parked[r.id] = (s, rows, r.c)
+                        self._held.add(s)
+                    else:
+                        self._active.discard(r.id)
                     retire = getattr(self.backend, "retire", None)
                     if retire is not None:
                         retire(s, r)
@@ -596,6 +678,8 @@ class ContinuousGenerator:
         self._plan = self._plan_ws = self._plan_params = self._admit_ws = None
         self._sampling = None   # (top_p, eos_id, sp2_id, seed) of the run in progress
         self.admit_calls = 0
+        self.extend_calls = 0
+        self._cap_host = [0] * mb   # the caption rows each slot was admitted with (extend's host check)
         if engine != "python":
             self._create_plan()
 
@@ -661,6 +745,15 @@ class ContinuousGenerator:
             L.check(n, "ergm_decode_admit_launches")
         return n
 
+    def extend_launches(self, n_seq: int, rows: int) -> int:
+        """Kernel launches of one native extension of these sizes (ergm_decode_extend_launches)."""
+        if self._plan is None:
+            raise ValueError("the python engine has no executor plan")
+        n = L.load().ergm_decode_extend_launches(self._plan, n_seq, rows)
+        if n < 0:
+            L.check(n, "ergm_decode_extend_launches")
+        return n
+
     # ---- admission --------------------------------------------------------------------------------------
     def _features(self, prompts):
         """(vis, aud) f32 [n_seq, E], projected when the features are wider or narrower than E (config 5), zeros for
@@ -709,6 +802,8 @@ class ContinuousGenerator:
         q0 = [sum(lens[:b]) for b in range(n_seq)]
         c0 = [sum(clens[:b]) for b in range(n_seq)]
         self.admit_calls += 1
+        for sl, c in zip(slots, clens):
+            self._cap_host[sl] = c
         if self.engine == "python":
             self._admit_python(slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has)
         else:
@@ -771,6 +866,100 @@ class ContinuousGenerator:
         L.call("ergm_decode_admit", self._plan, n_seq, arr(slots), arr(lens), arr(clens), arr(max_new), p(meta), p(ids), p(tt),
                p(cids), p(vis), p(aud), p(flags), p(self._admit_ws), self._admit_ws.numel(), self._stream())
 
+    # ---- extension: more than one token behind a cache that holds a past -------------------------------------
+    @torch.no_grad()
+    def extend(self, slots, turns, max_new_tokens=None, past=None) -> None:
+        """Append the tokens of ``turns`` (one (input_ids, token_type_ids) per slot) behind what the occupied ``slots``
+        hold, and leave the logits after each turn's last token in the slot (low level; ``extend_request`` / ``run``
+        do this through the scheduler).  The captions, the request ids and the draw counters stay those of the
+        admission.  max_new_tokens: one bound per turn (default: to the end of the cache).  past: the rows each slot
+        holds; None reads them from ``lens`` (one sync).  A slot's first two positions belong to its admission (they
+        may carry the visual / audio vectors), so every past is at least 2."""
+        self.m.refresh_bf16()
+        n_seq = len(turns)
+        slots = [int(s) for s in slots]
+        if len(slots) != n_seq or n_seq < 1:
+            raise ValueError("extend takes one slot per turn")
+        if len(set(slots)) != n_seq or min(slots) < 0 or max(slots) >= self.max_batch:
+            raise ValueError(f"slots {slots}: outside [0, {self.max_batch}) or named twice")
+        ids_l = [t[0].reshape(-1) for t in turns]
+        tt_l = [t[1].reshape(-1) for t in turns]
+        lens = [int(t.numel()) for t in ids_l]
+        if past is None:
+            host = self.lens.cpu().tolist()
+            past = [host[s] for s in slots]
+        past = [int(x) for x in past]
+        max_new = ([self.max_len - p - n for p, n in zip(past, lens)] if max_new_tokens is None
+                   else [int(x) for x in max_new_tokens])
+        clens = [self._cap_host[s] for s in slots]
+        if not (n_seq == len(past) == len(max_new)):
+            raise ValueError("extend takes one past and one bound per turn")
+        for tt, n, p, c, k in zip(tt_l, lens, past, clens, max_new):
+            if n < 1 or tt.numel() != n or p < 2 or c < 1 or k < 1 or p + n + k > self.max_len:
+                raise ValueError(f"a turn of {n} tokens ({tt.numel()} token types) behind {p} rows with {k} new tokens "
+                                 f"does not fit max_len {self.max_len}, or its slot was never admitted")
+        if sum(lens) > self.sched.max_admit_tokens or n_seq > self.sched.max_admit:
+            raise ValueError("more sequences or packed rows than one extension takes (max_admit, max_admit_tokens)")
+        q0 = [sum(lens[:b]) for b in range(n_seq)]
+        dev = self.dev
+        ids = torch.cat(ids_l).to(device=dev, dtype=torch.int64)
+        tt = torch.cat(tt_l).to(device=dev, dtype=torch.int64)
+        pos = torch.tensor([p + s for p, n in zip(past, lens) for s in range(n)], dtype=torch.int32).to(dev)
+        self.extend_calls += 1
+        if self.engine == "python":
+            self._extend_python(slots, ids, tt, pos, lens, past, clens, q0, max_new)
+        else:
+            self._extend_native(slots, ids, tt, pos, lens, past, clens, q0, max_new)
+
+    def _extend_python(self, slots, ids, tt, pos, lens, past, clens, q0, max_new) -> None:
+        """The yardstick: the row-wise kernels over the packed rows, the K | V rows copied by torch, and the attention
+        sequence by sequence through ergm_attn_fwd over the whole sequence (queries zero below ``past``, only the rows
+        from ``past`` kept), so that nothing here runs the extension's own kernels."""
+        E, H, dev, n_seq = self.E, self.H, self.dev, len(slots)
+        R = sum(lens)
+        h = ops.embed_rows(ids, tt, pos, self._f("__wte_pad"), self._f("transformer.wpe.weight"))
+        rows = [slice(q0[b], q0[b] + lens[b]) for b in range(n_seq)]
+        for l in range(self.L):
+            p = f"transformer.h.{l}."
+            x = self._ln(h, p + "ln_1")
+            qkv = self._gemm(x, p + "attn.c_attn", R, 3 * E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+            a = torch.empty(R, E, dtype=torch.bfloat16, device=dev)
+            for b, r in enumerate(rows):
+                n_all = past[b] + lens[b]
+                self.kv[l][slots[b], past[b]:n_all].copy_(qkv[r, E:])
+                qf = torch.zeros(n_all, E, dtype=torch.bfloat16, device=dev)
+                qf[past[b]:] = qkv[r, :E]
+                kvb = self.kv[l][slots[b], :n_all]
+                ob, _ = ops.attn_fwd(qf, kvb[:, :E], kvb[:, E:], 1, H, n_all, n_all, True)
+                a[r] = ob[past[b]:]
+            self._gemm(a, p + "attn.c_proj", R, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
+            x = self._ln(h, p + "ln_cross_attn")
+            q = self._gemm(x, p + "crossattention.q_attn", R, E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+            a = torch.empty(R, E, dtype=torch.bfloat16, device=dev)
+            for b, r in enumerate(rows):
+                kvb = self.xkv[l][slots[b], :clens[b]]
+                ops.attn_fwd(q[r], kvb[:, :E], kvb[:, E:], 1, H, lens[b], clens[b], False, o=a[r])
+            self._gemm(a, p + "crossattention.c_proj", R, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
+            self._mlp(p, h, R)
+        last = torch.tensor([q0[b] + lens[b] - 1 for b in range(n_seq)], device=dev)
+        sl = torch.tensor(slots, device=dev)
+        self._logits[sl] = self._head(h.index_select(0, last))
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+        self.lens[sl] = i32([p_ + n for p_, n in zip(past, lens)])
+        self.stop_lens[sl] = i32([p_ + n + k for p_, n, k in zip(past, lens, max_new)])
+        self.finished[sl] = 0
+
+    def _extend_native(self, slots, ids, tt, pos, lens, past, clens, q0, max_new) -> None:
+        n_seq = len(slots)
+        meta = torch.tensor([slots, q0, lens, past, [s * self.max_len for s in slots], [p + n for p, n in zip(past, lens)],
+                             [s * self.cap_max for s in slots], clens, max_new, [a + n - 1 for a, n in zip(q0, lens)],
+                             [1] * n_seq, list(range(n_seq))], dtype=torch.int32).to(self.dev)
+        assert meta.shape[0] == L.EXTEND_META_ROWS
+        arr = lambda v: (C.c_int * n_seq)(*v)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        L.call("ergm_decode_extend", self._plan, n_seq, arr(slots), arr(past), arr(lens), arr(clens), arr(max_new), p(meta),
+               p(ids), p(tt), p(pos), p(self._admit_ws), self._admit_ws.numel(), self._stream())
+
     # ---- decode -------------------------------------------------------------------------------------------
     @torch.no_grad()
     def step(self, tokens: torch.Tensor, token_types: torch.Tensor) -> torch.Tensor:
@@ -831,14 +1020,38 @@ class ContinuousGenerator:
     def admit_requests(self, slots, requests) -> None:
         self.admit(slots, [r.payload for r in requests], [r.max_new for r in requests], [r.id for r in requests])
 
+    def extend_requests(self, slots, requests) -> None:
+        self.extend(slots, [r.payload for r in requests], [r.max_new for r in requests], [r.past for r in requests])
+
     def retire(self, slot: int, request) -> None:
         if self.keep_logits:
             self.final_logits[request.id] = self.logits[slot].clone()
 
     # ---- requests -----------------------------------------------------------------------------------------
-    def submit(self, prompt, max_new_tokens: Optional[int] = None, request_id: Optional[int] = None) -> int:
-        """Queue a prompt; returns its id (uint32; arrival order unless given)."""
-        return self.sched.submit(int(prompt[0].numel()), int(prompt[2].numel()), max_new_tokens, request_id, prompt)
+    def submit(self, prompt, max_new_tokens: Optional[int] = None, request_id: Optional[int] = None,
+               keep: bool = False) -> int:
+        """Queue a prompt; returns its id (uint32; arrival order unless given).  ``keep``: the request keeps its slot
+        and its cache when it ends (it is parked), so that ``extend_request`` can continue the conversation; a kept
+        prompt that carries visual / audio features has at least 2 tokens (the positions the features sit at)."""
+        if keep and prompt[3] is not None and int(prompt[0].numel()) < 2:
+            raise ValueError("a kept prompt with visual / audio features needs at least 2 tokens")
+        return self.sched.submit(int(prompt[0].numel()), int(prompt[2].numel()), max_new_tokens, request_id, prompt, keep)
+
+    def extend_request(self, request_id: int, ids, token_types, max_new_tokens: Optional[int] = None,
+                       keep: bool = True) -> int:
+        """Queue the next turn of a parked request: ``ids`` / ``token_types`` are appended behind what its cache holds
+        (the tokens of the earlier turns; an eos the model drew is not among them, so a turn that wants it as a
+        separator begins with it), and up to max_new_tokens are generated behind them at the next ``run`` / ``drain``,
+        returned under the same id.  Raises ValueError when the id is not parked, the turn is empty or longer than
+        max_admit_tokens, or the cache has no room for it and one new token."""
+        ids, token_types = ids.reshape(-1), token_types.reshape(-1)
+        if ids.numel() != token_types.numel():
+            raise ValueError("one token type per token")
+        return self.sched.extend(request_id, int(ids.numel()), max_new_tokens, (ids, token_types), keep)
+
+    def release(self, request_id: int) -> None:
+        """Free the slot of a parked request."""
+        self.sched.release(request_id)
 
     def drain(self, top_p: float, eos_id: int, sp2_id: int, seed: int = 0):
         """Serve the queue, yielding (id, tokens) as each request retires."""

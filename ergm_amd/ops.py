@@ -427,6 +427,45 @@ def rows_to_slots(src, start, length, slot, max_rows: int, dst, n_slots: Optiona
     return dst
 
 
+def attn_fwd_extend(q, k, v, q_start, q_len, k_start, k_len, H: int, max_q: int, max_k: int, o=None):
+    """Causal attention of packed new query rows over caches that already hold a past, in one launch
+    (ergm_attn_fwd_extend).  ``attn_fwd_ragged``'s arguments; k_len[b] >= q_len[b], query row s of sequence b sits at
+    position k_len[b] - q_len[b] + s and sees the keys up to it, and the new rows' own K / V are already among the key
+    rows.  Row s is bitwise row past + s of ``attn_fwd(B=1, Sq=Sk=k_len[b], causal)``.  Returns ``o``."""
+    _need_gpu(q, k, v, q_start, q_len, k_start, k_len)
+    assert q.dtype == k.dtype == v.dtype == torch.bfloat16
+    for t in (q_start, q_len, k_start, k_len):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == q_start.numel()
+    dev = q.device
+    if o is None:
+        o = torch.empty(q.shape[0], H * 64, dtype=torch.bfloat16, device=dev)
+    L.call("ergm_attn_fwd_extend", _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(q_start), _ptr(q_len), _ptr(k_start),
+           _ptr(k_len), q_start.numel(), H, q.shape[0], k.shape[0], max_q, max_k, q.stride(0), k.stride(0), v.stride(0),
+           o.stride(0), _stream(dev))
+    return o
+
+
+def rows_to_slots_at(src, start, length, slot, dst_row0, max_rows: int, dst, n_slots: Optional[int] = None,
+                     slot_rows: Optional[int] = None):
+    """``rows_to_slots`` with a first destination row per sequence: row t < length[b] of sequence b -> dst[slot[b],
+    dst_row0[b] + t] (ergm_rows_to_slots_at); a sequence stops at the slot's last row."""
+    _need_gpu(src, start, length, slot, dst_row0, dst)
+    assert src.dtype == dst.dtype and src.dim() == 2 and src.stride(1) == 1 and dst.stride(-1) == 1
+    for t in (start, length, slot, dst_row0):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == start.numel()
+    es = src.element_size()
+    if dst.dim() == 2:
+        ld_slot, ld_row, rows = dst.stride(0), dst.stride(0), 1
+    else:
+        ld_slot, ld_row, rows = dst.stride(0), dst.stride(1), dst.shape[1]
+    if src.shape[1] != dst.shape[-1]:
+        raise ValueError("rows_to_slots_at: src and dst rows differ in width")
+    L.call("ergm_rows_to_slots_at", _ptr(src), src.stride(0) * es, _ptr(start), _ptr(length), _ptr(slot), _ptr(dst_row0),
+           start.numel(), src.shape[0], max_rows, _ptr(dst), ld_slot * es, ld_row * es, src.shape[1] * es,
+           dst.shape[0] if n_slots is None else n_slots, rows if slot_rows is None else slot_rows, _stream(src.device))
+    return dst
+
+
 def embed_packed(ids, tt, cap_ids, wte, wpe, q_start, q_len, c_start, c_len, max_rows: int, max_cap: int, vis=None,
                  aud=None, has_feat=None):
     """ergm_embed_fwd for packed rows (ergm_embed_packed): ids / tt int64 [Σ n_b], cap_ids int64 [Σ c_b], the starts

@@ -25,6 +25,7 @@
  *   ergm_adamw_step       torch.optim.AdamW.step (src/main.py:68,155)
  *   ergm_attn_decode, ergm_embed_rows, ergm_topp_sample,
  *   ergm_attn_fwd_ragged, ergm_embed_packed, ergm_rows_to_slots, ergm_topp_sample_rows
+ *   ergm_attn_fwd_extend, ergm_rows_to_slots_at, ergm_decode_extend (later additions, same version)
  *                         the per-token work of nucleus_sampling (src/main.py:253-282), for a batch
  *   ergm_linear_rows      Conv1D / lm_head for the few rows of a decode step, with the nn.LayerNorm in front
  *                         of it (src/model.py:298,318,332) computed in the same launch
@@ -248,6 +249,20 @@ int ergm_attn_fwd_ragged(const void* q, const void* k, const void* v, void* o, f
                          const int* q_len, const int* k_start, const int* k_len, int n_seq, int H, int total_q,
                          int total_k, int max_q, int max_k, int ldq, int ldk, int ldv, int ldo, int causal,
                          void* stream);
+/* Causal inference attention of packed NEW query rows over caches that already hold a past, one launch (found by
+ * symbol; the ABI version is unchanged).  ergm_attn_fwd_ragged's arguments without lse and causal; the mask is aligned
+ * to the bottom-right corner: sequence b owns query rows q_start[b] .. q_start[b] + q_len[b] - 1 of q / o and key rows
+ * k_start[b] .. k_start[b] + k_len[b] - 1 of k / v with k_len[b] >= q_len[b]; past_b = k_len[b] - q_len[b]; query row s
+ * is position past_b + s and sees keys 0 .. past_b + s.  The new rows' own K / V must already be among the key rows
+ * (ergm_rows_to_slots_at).  With a layer's slot cache as k / v: k_start[b] = slot_b · max_len, total_k = max_batch ·
+ * max_len, ldk = ldv = 2 · n_embd.  Query tiles are counted in absolute positions (tile t = positions 64t .. 64t + 63,
+ * a sequence runs tiles past_b / 64 .. ceil(k_len[b] / 64) - 1; grid (ceil(max_q / 64) + 1, H, n_seq)), so that output
+ * row s is bitwise row past_b + s of ergm_attn_fwd(B = 1, Sq = Sk = k_len[b], causal = 1) over the sequence alone.
+ * Every value read from the arrays is clamped to [0, max] and the packed extents before an address is formed, q_len to
+ * k_len, and no row outside a sequence's own query rows is read from q or written to o.                            */
+int ergm_attn_fwd_extend(const void* q, const void* k, const void* v, void* o, const int* q_start, const int* q_len,
+                         const int* k_start, const int* k_len, int n_seq, int H, int total_q, int total_k, int max_q,
+                         int max_k, int ldq, int ldk, int ldv, int ldo, void* stream);
 /* delta workspace: B*H*Sq floats.  dq/dk/dv are bf16 with their own leading dims.              */
 int ergm_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,
                   const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int H, int Sq,
@@ -366,6 +381,12 @@ int ergm_topp_sample_rows(const float* logits, int ldl, int B, int V, float top_
 int ergm_rows_to_slots(const void* src, int64_t ld_src, const int* start, const int* len, const int* slot, int n_seq,
                        int total_rows, int max_rows, void* dst, int64_t ld_slot, int64_t ld_row, int row_bytes,
                        int n_slots, int slot_rows, void* stream);
+/* ergm_rows_to_slots with a first destination row per sequence: row t goes to slot row dst_row0[b] + t (device int
+ * [n_seq]).  dst_row0 is clamped to [0, slot_rows] and len to the rows left after it, so nothing lands at or past
+ * slot_rows.  With every dst_row0[b] = 0 the result is ergm_rows_to_slots'.  Found by symbol (ABI unchanged).      */
+int ergm_rows_to_slots_at(const void* src, int64_t ld_src, const int* start, const int* len, const int* slot,
+                          const int* dst_row0, int n_seq, int total_rows, int max_rows, void* dst, int64_t ld_slot,
+                          int64_t ld_row, int row_bytes, int n_slots, int slot_rows, void* stream);
 /* ergm_embed_fwd for packed rows of n_seq sequences of different lengths: token row s < q_len[b] of sequence b (packed
  * row q_start[b] + s of ids / tt / h0) is ((wte[id] + [s==0]·vis[b] + [s==1]·aud[b]) + wpe[s]) + wte[tt], in that
  * kernel's summation order: bitwise the row ergm_embed_fwd(B = 1, S = q_len[b]) writes.  Caption row s < c_len[b]
@@ -744,6 +765,32 @@ int ergm_decode_admit(ergm_decode_plan* plan, int n_seq, const int* slots, const
 /* Kernel launches of one ergm_decode_admit of n_seq sequences with `rows` packed token rows and `cap_rows` packed
  * caption rows, counted by walking the admission's own launch sequence dry.  Host only.                          */
 int ergm_decode_admit_launches(const ergm_decode_plan* plan, int n_seq, int rows, int cap_rows);
+#define ERGM_EXTEND_META_ROWS 12
+/* Extends n_seq OCCUPIED slots by n_b >= 1 new tokens each (a later turn of a conversation; found by symbol, the ABI
+ * version is unchanged), on the admission's workspace (ergm_decode_admit_workspace_size; max_cap_rows is not used):
+ * ergm_embed_rows over the R = Σ n_b packed rows at their own positions; per layer LayerNorm, the qkv GEMM over the
+ * packed rows, ergm_rows_to_slots_at of the K | V columns to rows past_b .. of the slot, ergm_attn_fwd_extend over the
+ * slot's cache, the projection, LayerNorm, the q GEMM, ergm_attn_fwd_ragged(causal = 0) over the caption rows the
+ * admission left in the slot (xkv[l] as packed rows; no caption GEMM runs), the projection, the MLP; then the last new
+ * row of every sequence through ln_f and the head into logits[slot]; then one kernel sets lens = past_b + n_b,
+ * stop_lens = past_b + n_b + max_new and finished = 0 of every slot extended, and leaves cap_lens, row_ids and
+ * row_steps alone: the request goes on drawing from fresh Philox counters.  12 launches per block + 6 when no GEMM
+ * splits, whatever n_seq is.
+ *   slots, past, lens (= n_b), cap_lens, max_new: HOST int [n_seq], checked here; ERGM_EINVAL before any launch for a
+ *     slot outside [0, max_batch) or named twice, n_b < 1, past_b < 2 (positions 0 and 1 may carry the admission's
+ *     visual / audio vectors), c_b outside [1, cap_max], max_new < 1, past_b + n_b + max_new > max_len, or more packed
+ *     rows than the workspace holds.  past_b and c_b are the caller's record of the slot's lens and cap_lens.
+ *   meta: DEVICE int [ERGM_EXTEND_META_ROWS][n_seq], what the kernels read (each value clamped before use): rows
+ *     0 slot, 1 first packed row, 2 n_b, 3 past_b, 4 slot · max_len (first key row), 5 past_b + n_b (key rows),
+ *     6 slot · cap_max (first caption row), 7 c_b, 8 max_new, 9 last packed row (row 1 + row 2 - 1), 10 all ones,
+ *     11 0 .. n_seq-1.
+ *   ids, token_types (may be NULL): device int64 [R]; pos: device int [R], past_b + s for row s of sequence b.      */
+int ergm_decode_extend(ergm_decode_plan* plan, int n_seq, const int* slots, const int* past, const int* lens,
+                       const int* cap_lens, const int* max_new, const int* meta, const int64_t* ids,
+                       const int64_t* token_types, const int* pos, void* workspace, size_t ws_bytes, void* stream);
+/* Kernel launches of one ergm_decode_extend of n_seq sequences with `rows` packed rows, counted by walking the
+ * extension's own launch sequence dry.  Host only.                                                               */
+int ergm_decode_extend_launches(const ergm_decode_plan* plan, int n_seq, int rows);
 /* One step over all max_batch slots (ergm_decode_step's kernels at B = max_batch, caption bound cap_max), then the
  * slot length update: a row not finished gets ++lens, ++row_steps, and finished = 1 when lens reaches stop_lens, so
  * no row can pass the bound recorded at its admission (n_b + max_new <= max_len) whatever the host does.          */

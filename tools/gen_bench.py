@@ -26,11 +26,17 @@ tokens (the sum of the list) over the whole call, and ``steps_per_token`` = deco
   admit           one admission of n_seq = 1, 4, 8, 32 such prompts: milliseconds on engines "python" and "native" and
                   the native launch count; and the ragged attention launch against the n_seq ergm_attn_fwd launches it
                   replaces (causal, 64 rows each, H = 12), microseconds per call in back-to-back windows of 100
+Conversations, ``turns``: 32 sessions of 4 turns, a 64-token first prompt, 16-token later turns and 16
+new tokens per turn, on ContinuousGenerator(max_batch=32, max_len=192), engines "native" and "fused":
+  continue   submit(keep=True), then extend_request per turn: each turn prefills its 16 new rows over the parked cache
+  resubmit   what a user does without it: every turn is a new request carrying the whole history (the baseline)
+tokens/s = the 2,048 requested tokens over the four turns of all sessions, the two ways alternating in one process,
+median of 5 after a warm-up each; ``prefill_rows`` = the packed rows each turn's prefill ran over.
 Without --case the tool runs every case in turn, each in a fresh child process under its own timeout, one at a
 time, and stops at the first that fails.  --cases a,b,c runs those cases in that
 order (e.g. b32,n32,f32,b32,n32,f32 to alternate engines on one box).  For the kernel-time split of one engine:
   rocprofv3 --kernel-trace --stats -d OUT -- python tools/gen_bench.py --case f32
-Usage (GPU box): python tools/gen_bench.py [--case kv|b1|b8|b32|n*|f*|attn|bs32|bc32|n?32|f?32|admit] [--cases LIST]"""
+Usage (GPU box): python tools/gen_bench.py [--case kv|b1|b8|b32|n*|f*|attn|bs32|bc32|n?32|f?32|admit|turns] [--cases LIST]"""
 import json
 import os
 import statistics
@@ -41,7 +47,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 ENGINES = {"b": "python", "n": "native", "f": "fused"}
 CASES = {"kv": 240, **{e + b: 240 for e in ENGINES for b in ("1", "8", "32")}, "attn": 240,   # seconds a child may take
-         **{e + m + "32": 300 for e in ENGINES for m in "sc"}, "admit": 240}
+         **{e + m + "32": 300 for e in ENGINES for m in "sc"}, "admit": 240, "turns": 420}
 N_REQ, REQ_MEAN = 256, 16
 PROMPT = CAPS = NEW = 64
 TOP_P, NO_EOS, SP2 = 0.95, -1, 50259
@@ -177,6 +183,65 @@ def _admission():
         print(json.dumps(row), flush=True)
 
 
+SESSIONS, TURNS, TURN_ROWS, TURN_NEW = 32, 4, 16, 16
+
+
+def _turns():
+    import torch
+    from ergm_amd.generate import ContinuousGenerator
+    dev, model, prompts, _ = _setup_requests(SESSIONS)
+    g = torch.Generator().manual_seed(3)
+    later = [[(torch.randint(0, 50000, (TURN_ROWS,), generator=g).to(dev), torch.full((TURN_ROWS,), SP2 - 1, device=dev))
+              for _ in range(SESSIONS)] for _ in range(TURNS - 1)]
+    max_len = PROMPT + TURN_NEW + (TURNS - 1) * (TURN_ROWS + TURN_NEW)
+    max_len = (max_len + 63) // 64 * 64
+    for engine in ("native", "fused"):
+        gen = ContinuousGenerator(model, max_batch=SESSIONS, max_len=max_len, cap_max=CAPS, engine=engine)
+        rows = {"continue": [], "resubmit": []}
+        sample = dict(top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2, seed=7)
+
+        def run_continue():
+            rows["continue"] = [SESSIONS * PROMPT] + [SESSIONS * TURN_ROWS] * (TURNS - 1)
+            ids = [gen.submit(p, TURN_NEW, keep=True) for p in prompts]
+            out = gen.run(**sample)
+            for t in range(TURNS - 1):
+                for i, (x, tt) in zip(ids, later[t]):
+                    gen.extend_request(i, x, tt, TURN_NEW)
+                out = gen.run(**sample)
+                assert all(len(out[i]) == TURN_NEW for i in ids)
+            for i in ids:
+                gen.release(i)
+
+        def run_resubmit():
+            hist = [(p[0], p[1]) for p in prompts]
+            rows["resubmit"] = []
+            for t in range(TURNS):
+                if t:
+                    hist = [(torch.cat([h[0], torch.tensor([new[i]], device=dev), later[t - 1][b][0].view(1, -1)], 1),
+                             torch.cat([h[1], torch.full((1, TURN_NEW), SP2, device=dev), later[t - 1][b][1].view(1, -1)], 1))
+                            for b, (h, i) in enumerate(zip(hist, ids))]
+                rows["resubmit"].append(sum(int(h[0].numel()) for h in hist))
+                ids = [gen.submit((h[0], h[1], p[2], None, None), TURN_NEW) for h, p in zip(hist, prompts)]
+                new = gen.run(**sample)
+                assert all(len(new[i]) == TURN_NEW for i in ids)
+
+        ms = {"continue": [], "resubmit": []}
+        for rep in range(REPEATS + 1):   # alternating; the first of each is the warm-up
+            for name, fn in (("continue", run_continue), ("resubmit", run_resubmit)):
+                t = _event_ms(fn)
+                if rep:
+                    ms[name].append(t)
+        tokens = SESSIONS * TURNS * TURN_NEW
+        row = {"case": "turns", "engine": engine, "sessions": SESSIONS, "turns": TURNS, "requested_tokens": tokens,
+               "extend_launches": gen.extend_launches(SESSIONS, SESSIONS * TURN_ROWS)}
+        for name in ms:
+            med = statistics.median(ms[name])
+            row[name] = {"ms_median": round(med, 2), "ms_all": [round(x, 2) for x in ms[name]],
+                         "tokens_per_s": round(tokens / med * 1e3, 1), "prefill_rows": rows[name]}
+        row["speedup"] = round(statistics.median(ms["resubmit"]) / statistics.median(ms["continue"]), 3)
+        print(json.dumps(row), flush=True)
+
+
 def _attention():
     import torch
     from ergm_amd import ops
@@ -215,6 +280,8 @@ def main():
             _attention()
         elif case == "admit":
             _admission()
+        elif case == "turns":
+            _turns()
         elif len(case) == 4 and case[1] in "sc":
             _requests(case)
         else:
