@@ -223,35 +223,44 @@ class BatchedGenerator:
         except Exception:
             pass
 
+    def _new_plan(self, cap_max: int, capkv: bool):
+        """Create the executor plan (``_plan``, with its workspace and parameter block kept alive beside it) for
+        captions of up to cap_max rows, on this generator's engine; ``capkv`` passes the caption K/V weights, which
+        only an admission reads.  Returns the dimensions it was created with."""
+        lib, lay = L.load(), self.m.layout
+        dims = L.DecodeDims(vocab=lay.vocab, vocab_pad=lay.vocab_pad, n_embd=self.E, n_layer=self.L, n_head=self.H,
+                            n_inner=self.F, n_positions=self.cfg.n_positions, max_batch=self.max_batch,
+                            max_len=self.max_len, cap_max=cap_max, eps=self.cfg.layer_norm_epsilon)
+        prm = L.ModelParams()
+        prm.wte, prm.wte_b = self._f("__wte_pad").data_ptr(), self._b("__wte_pad").data_ptr()
+        prm.wpe = self._f("transformer.wpe.weight").data_ptr()
+        prm.ln_f_w = self._f("transformer.ln_f.weight").data_ptr()
+        prm.ln_f_b = self._f("transformer.ln_f.bias").data_ptr()
+        if capkv:
+            prm.capkv_w_b, prm.capkv_b = self._b("__capkv_w").data_ptr(), self._f("__capkv_b").data_ptr()
+        prm.layer_f32 = self.m.flat.data_ptr() + 4 * lay.layer_base[0]
+        prm.layer_b16 = self.m.flat_b16.data_ptr() + 2 * lay.layer_base[0]
+        prm.layer_stride = lay.layer_stride
+        for i, o in enumerate(lay.layer_off):
+            prm.layer_off[i] = o
+        need = lib.ergm_decode_workspace_size(C.byref(dims))
+        if need == 0:
+            raise ValueError("the decode executor does not support this model's dimensions")
+        self._plan_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        self._plan_params = prm
+        plan = C.c_void_p()
+        L.check(lib.ergm_decode_create(C.byref(dims), C.byref(prm), C.c_void_p(self._plan_ws.data_ptr()), need,
+                                       C.byref(plan)), "ergm_decode_create")
+        self._plan = plan
+        L.call("ergm_decode_set_engine", plan, self.ENGINES[self.engine])
+        return dims
+
     def _bind_plan(self, Sc: int) -> None:
         """(Re)create the executor plan when the captions outgrow it, then bind the state the prefill left."""
-        lib, lay = L.load(), self.m.layout
         if self._plan is None or Sc > self._cap_max:
             self._drop_plan()
             self._cap_max = max(Sc, self.max_len)
-            dims = L.DecodeDims(vocab=lay.vocab, vocab_pad=lay.vocab_pad, n_embd=self.E, n_layer=self.L, n_head=self.H,
-                                n_inner=self.F, n_positions=self.cfg.n_positions, max_batch=self.max_batch,
-                                max_len=self.max_len, cap_max=self._cap_max, eps=self.cfg.layer_norm_epsilon)
-            prm = L.ModelParams()
-            prm.wte, prm.wte_b = self._f("__wte_pad").data_ptr(), self._b("__wte_pad").data_ptr()
-            prm.wpe = self._f("transformer.wpe.weight").data_ptr()
-            prm.ln_f_w = self._f("transformer.ln_f.weight").data_ptr()
-            prm.ln_f_b = self._f("transformer.ln_f.bias").data_ptr()
-            prm.layer_f32 = self.m.flat.data_ptr() + 4 * lay.layer_base[0]
-            prm.layer_b16 = self.m.flat_b16.data_ptr() + 2 * lay.layer_base[0]
-            prm.layer_stride = lay.layer_stride
-            for i, o in enumerate(lay.layer_off):
-                prm.layer_off[i] = o
-            need = lib.ergm_decode_workspace_size(C.byref(dims))
-            if need == 0:
-                raise ValueError("the decode executor does not support this model's dimensions")
-            self._plan_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-            self._plan_params = prm
-            plan = C.c_void_p()
-            L.check(lib.ergm_decode_create(C.byref(dims), C.byref(prm), C.c_void_p(self._plan_ws.data_ptr()), need,
-                                           C.byref(plan)), "ergm_decode_create")
-            self._plan = plan
-            L.call("ergm_decode_set_engine", self._plan, self.ENGINES[self.engine])
+            self._new_plan(self._cap_max, capkv=False)
         ptrs = C.c_void_p * self.L
         kv = ptrs(*[t.data_ptr() for t in self.kv])
         xkv = ptrs(*[t.data_ptr() for t in self.xkv])
@@ -268,6 +277,59 @@ class BatchedGenerator:
         act = self._gemm(x, p + "mlp.c_fc", n, self.F, self.E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS_GELU,
                          aux_out=pre)
         self._gemm(act, p + "mlp.c_proj", n, self.E, self.F, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
+
+    def _block(self, l: int, h: torch.Tensor, n: int, self_attn, cross_attn) -> None:
+        """The n rows of h [n, E] through block l, in place: the one place the "python" engine of the batch generators
+        spells the block out.  The caller supplies the two stages that differ between prefill, admission, extension
+        and step: ``self_attn(l, qkv)`` takes the rows' q | k | v [n, 3E], writes their K | V to the cache and returns
+        the attention output [n, E] bf16; ``cross_attn(l, q)`` takes the cross query [n, E] and returns the attention
+        over the captions."""
+        E = self.E
+        p = f"transformer.h.{l}."
+        x = self._ln(h, p + "ln_1")
+        qkv = self._gemm(x, p + "attn.c_attn", n, 3 * E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+        a = self_attn(l, qkv)
+        self._gemm(a, p + "attn.c_proj", n, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
+        x = self._ln(h, p + "ln_cross_attn")
+        q = self._gemm(x, p + "crossattention.q_attn", n, E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+        a = cross_attn(l, q)
+        self._gemm(a, p + "crossattention.c_proj", n, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
+        self._mlp(p, h, n)
+
+    def _step_rows(self, tokens, token_types, lens, cap_lens, kv, xkv) -> torch.Tensor:
+        """The "python" engine's step: one token per sequence at position lens[b], through every block over the
+        per-layer caches kv [B, max_len, 2E] (the new K | V row appended) and xkv [B, Sc, 2E].  Returns the logits
+        [B, vocab_pad]; the caller updates its own state."""
+        E, ws = self.E, self._ws
+        h = ops.embed_rows(tokens, token_types, lens, self._f("__wte_pad"), self._f("transformer.wpe.weight"))
+
+        def self_attn(l, qkv):
+            return ops.attn_decode(qkv, kv[l][:, :, :E], kv[l][:, :, E:], lens, True, ws=ws)
+
+        def cross_attn(l, q):
+            return ops.attn_decode(q, xkv[l][:, :, :E], xkv[l][:, :, E:], cap_lens, False, ws=ws)
+
+        for l in range(self.L):
+            self._block(l, h, h.shape[0], self_attn, cross_attn)
+        return self._head(h)
+
+    def _features(self, prompts):
+        """(vis, aud) f32 [n_seq, E], projected when the features are wider or narrower than E (config 5), zeros for
+        the sequences without features, and the per-sequence flags; (None, None, flags) when no prompt has features."""
+        has = [p[3] is not None for p in prompts]
+        if not any(has):
+            return None, None, has
+        n, Fd, dev = len(prompts), self.m.layout.Fd, self.dev
+        vis = torch.zeros(n, Fd, dtype=torch.float32, device=dev)
+        aud = torch.zeros(n, Fd, dtype=torch.float32, device=dev)
+        for b, p in enumerate(prompts):
+            if has[b]:
+                vis[b] = p[3].float().reshape(-1, Fd)[0]
+                aud[b] = p[4].float().reshape(Fd)
+        if Fd != self.E:
+            vis, aud = (self._gemm(x.to(torch.bfloat16), f"transformer.{m}", n, self.E, Fd, out_dtype=torch.float32,
+                                   epilogue=L.EPI_BIAS) for x, m in ((vis, "visual_proj"), (aud, "audio_proj")))
+        return vis, aud, has
 
     def _head(self, h_last: torch.Tensor) -> torch.Tensor:
         """Rows [B, E] -> logits [B, vocab_pad] f32 (the first ``vocab`` columns count)."""
@@ -301,41 +363,30 @@ class BatchedGenerator:
             tt[b, :lens[b]] = p[1].reshape(-1)
             cap_ids[b, :clens[b]] = cap_l[b]
         wte, wpe = self._f("__wte_pad"), self._f("transformer.wpe.weight")
-        Fd = self.m.layout.Fd
-        has = [p[3] is not None for p in prompts]
-        vis = aud = None
-        if any(has):   # sequences without features add zeros
-            vis = torch.zeros(B, Fd, dtype=torch.float32, device=dev)
-            aud = torch.zeros(B, Fd, dtype=torch.float32, device=dev)
-            for b, p in enumerate(prompts):
-                if has[b]:
-                    vis[b] = p[3].float().reshape(-1, Fd)[0]
-                    aud[b] = p[4].float().reshape(Fd)
-            if Fd != E:  # config 5: the build-side projections (Conv1D), then nothing for the rows without features
-                keep = torch.tensor(has, device=dev).unsqueeze(1)
-                vis, aud = (self._gemm(x.to(torch.bfloat16), f"transformer.{m}", B, E, Fd, out_dtype=torch.float32,
-                                       epilogue=L.EPI_BIAS) * keep for x, m in ((vis, "visual_proj"), (aud, "audio_proj")))
+        vis, aud, has = self._features(prompts)   # sequences without features add zeros
+        if vis is not None and self.m.layout.Fd != E:   # config 5: nothing for the rows without features
+            keep = torch.tensor(has, device=dev).unsqueeze(1)
+            vis, aud = vis * keep, aud * keep
         h, _ = ops.embed_fwd(ids, tt, ids, wte, wpe, vis, aud)
         _, cap = ops.embed_fwd(cap_ids, None, cap_ids, wte, wpe)
         self.xkv = [self._gemm(cap, f"transformer.h.{l}.crossattention.c_attn", B * Sc, 2 * E, E,
                                out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS).view(B, Sc, 2 * E) for l in range(self.L)]
         n = B * S
-        for l in range(self.L):
-            p = f"transformer.h.{l}."
-            x = self._ln(h, p + "ln_1")
-            qkv = self._gemm(x, p + "attn.c_attn", n, 3 * E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+
+        def self_attn(l, qkv):
             self.kv[l][:B, :S].copy_(qkv[:, E:].view(B, S, 2 * E))
-            a, _ = ops.attn_fwd(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], B, H, S, S, True)
-            self._gemm(a, p + "attn.c_proj", n, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
-            x = self._ln(h, p + "ln_cross_attn")
-            q = self._gemm(x, p + "crossattention.q_attn", n, E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+            return ops.attn_fwd(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], B, H, S, S, True)[0]
+
+        def cross_attn(l, q):
             a = torch.empty(n, E, dtype=torch.bfloat16, device=dev)
             for b in range(B):   # each sequence over its own caption rows: padded caption rows are never attended
                 kvb = self.xkv[l][b, :clens[b]]
                 ops.attn_fwd(q[b * S:(b + 1) * S], kvb[:, :E], kvb[:, E:], 1, H, S, clens[b], False,
                              o=a[b * S:(b + 1) * S])
-            self._gemm(a, p + "crossattention.c_proj", n, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
-            self._mlp(p, h, n)
+            return a
+
+        for l in range(self.L):
+            self._block(l, h, n, self_attn, cross_attn)
         self.B, self.n_max = B, S
         self.lens[:B] = torch.tensor(lens, dtype=torch.int32, device=dev)
         self.cap_lens[:B] = torch.tensor(clens, dtype=torch.int32, device=dev)
@@ -355,7 +406,7 @@ class BatchedGenerator:
             raise ValueError("step before prefill")
         if self.n_max >= self.max_len:
             raise ValueError("KV cache full")
-        B, E, dev = self.B, self.E, self.dev
+        B = self.B
         tokens, token_types = tokens.reshape(-1), token_types.reshape(-1)
         if tokens.numel() != B or token_types.numel() != B:
             raise ValueError(f"step takes one token and one token type per sequence ({B})")
@@ -367,22 +418,8 @@ class BatchedGenerator:
                    self._stream())
             self.n_max += 1
             return self._logits[:, :self.m.layout.vocab]
-        lens, cap_lens = self.lens[:B], self.cap_lens[:B]
-        h = ops.embed_rows(tokens, token_types, lens, self._f("__wte_pad"), self._f("transformer.wpe.weight"))
-        for l in range(self.L):
-            p = f"transformer.h.{l}."
-            x = self._ln(h, p + "ln_1")
-            qkv = self._gemm(x, p + "attn.c_attn", B, 3 * E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
-            cache = self.kv[l][:B]
-            a = ops.attn_decode(qkv, cache[:, :, :E], cache[:, :, E:], lens, True, ws=self._ws)
-            self._gemm(a, p + "attn.c_proj", B, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
-            x = self._ln(h, p + "ln_cross_attn")
-            q = self._gemm(x, p + "crossattention.q_attn", B, E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
-            xkv = self.xkv[l]
-            a = ops.attn_decode(q, xkv[:, :, :E], xkv[:, :, E:], cap_lens, False, ws=self._ws)
-            self._gemm(a, p + "crossattention.c_proj", B, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
-            self._mlp(p, h, B)
-        self._logits = self._head(h)
+        lens = self.lens[:B]
+        self._logits = self._step_rows(tokens, token_types, lens, self.cap_lens[:B], [t[:B] for t in self.kv], self.xkv)
         lens.add_((self.finished[:B] == 0).to(torch.int32))
         self.n_max += 1
         return self._logits[:, :self.m.layout.vocab]
@@ -686,14 +723,8 @@ class ContinuousGenerator:
     _f, _b, _ln = KVCacheGenerator._f, KVCacheGenerator._b, KVCacheGenerator._ln
     _gemm, _mlp, _head, _stream = (BatchedGenerator._gemm, BatchedGenerator._mlp, BatchedGenerator._head,
                                    BatchedGenerator._stream)
-
-    def __del__(self):
-        try:
-            plan, self._plan = self._plan, None
-            if plan is not None:
-                L.load().ergm_decode_destroy(plan)
-        except Exception:
-            pass
+    _block, _step_rows, _features = BatchedGenerator._block, BatchedGenerator._step_rows, BatchedGenerator._features
+    _new_plan, _drop_plan, __del__ = BatchedGenerator._new_plan, BatchedGenerator._drop_plan, BatchedGenerator.__del__
 
     @property
     def logits(self) -> torch.Tensor:
@@ -701,35 +732,14 @@ class ContinuousGenerator:
         return self._logits[:, :self.m.layout.vocab]
 
     def _create_plan(self) -> None:
-        lib, lay = L.load(), self.m.layout
         self.m.refresh_bf16()
-        dims = L.DecodeDims(vocab=lay.vocab, vocab_pad=lay.vocab_pad, n_embd=self.E, n_layer=self.L, n_head=self.H,
-                            n_inner=self.F, n_positions=self.cfg.n_positions, max_batch=self.max_batch,
-                            max_len=self.max_len, cap_max=self.cap_max, eps=self.cfg.layer_norm_epsilon)
-        prm = L.ModelParams()
-        prm.wte, prm.wte_b = self._f("__wte_pad").data_ptr(), self._b("__wte_pad").data_ptr()
-        prm.wpe = self._f("transformer.wpe.weight").data_ptr()
-        prm.ln_f_w = self._f("transformer.ln_f.weight").data_ptr()
-        prm.ln_f_b = self._f("transformer.ln_f.bias").data_ptr()
-        prm.capkv_w_b, prm.capkv_b = self._b("__capkv_w").data_ptr(), self._f("__capkv_b").data_ptr()
-        prm.layer_f32 = self.m.flat.data_ptr() + 4 * lay.layer_base[0]
-        prm.layer_b16 = self.m.flat_b16.data_ptr() + 2 * lay.layer_base[0]
-        prm.layer_stride = lay.layer_stride
-        for i, o in enumerate(lay.layer_off):
-            prm.layer_off[i] = o
-        need = lib.ergm_decode_workspace_size(C.byref(dims))
+        dims = self._new_plan(self.cap_max, capkv=True)
+        plan = self._plan
         rows = min(self.sched.max_admit_tokens, self.max_batch * self.max_len)
-        need_admit = lib.ergm_decode_admit_workspace_size(C.byref(dims), rows, self.sched.max_admit * self.cap_max)
-        if need == 0 or need_admit == 0:
+        need_admit = L.load().ergm_decode_admit_workspace_size(C.byref(dims), rows, self.sched.max_admit * self.cap_max)
+        if need_admit == 0:
             raise ValueError("the decode executor does not support this model's dimensions")
-        self._plan_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
         self._admit_ws = torch.empty(need_admit, dtype=torch.uint8, device=self.dev)
-        self._plan_params = prm
-        plan = C.c_void_p()
-        L.check(lib.ergm_decode_create(C.byref(dims), C.byref(prm), C.c_void_p(self._plan_ws.data_ptr()), need,
-                                       C.byref(plan)), "ergm_decode_create")
-        self._plan = plan
-        L.call("ergm_decode_set_engine", plan, self.ENGINES[self.engine])
         ptrs = C.c_void_p * self.L
         p = lambda t: C.c_void_p(t.data_ptr())
         L.call("ergm_decode_bind_slots", plan, ptrs(*[t.data_ptr() for t in self.kv]),
@@ -755,24 +765,6 @@ class ContinuousGenerator:
         return n
 
     # ---- admission --------------------------------------------------------------------------------------
-    def _features(self, prompts):
-        """(vis, aud) f32 [n_seq, E], projected when the features are wider or narrower than E (config 5), zeros for
-        the sequences without features, and the per-sequence flags; (None, None, flags) when no prompt has features."""
-        has = [p[3] is not None for p in prompts]
-        if not any(has):
-            return None, None, has
-        n, Fd, dev = len(prompts), self.m.layout.Fd, self.dev
-        vis = torch.zeros(n, Fd, dtype=torch.float32, device=dev)
-        aud = torch.zeros(n, Fd, dtype=torch.float32, device=dev)
-        for b, p in enumerate(prompts):
-            if has[b]:
-                vis[b] = p[3].float().reshape(-1, Fd)[0]
-                aud[b] = p[4].float().reshape(Fd)
-        if Fd != self.E:
-            vis, aud = (self._gemm(x.to(torch.bfloat16), f"transformer.{m}", n, self.E, Fd, out_dtype=torch.float32,
-                                   epilogue=L.EPI_BIAS) for x, m in ((vis, "visual_proj"), (aud, "audio_proj")))
-        return vis, aud, has
-
     @torch.no_grad()
     def admit(self, slots, prompts, max_new_tokens=None, request_ids=None) -> None:
         """Prefill ``prompts`` into the free ``slots`` (low level; ``submit`` / ``run`` do this through the scheduler).
@@ -822,25 +814,24 @@ class ContinuousGenerator:
             v, a = (vis[b:b + 1], aud[b:b + 1]) if has[b] else (None, None)
             h[rows[b]], _ = ops.embed_fwd(ids, tt_l[b].view(1, -1), ids, wte, wpe, v, a)
             _, cap[crows[b]] = ops.embed_fwd(cids, None, cids, wte, wpe)
-        for l in range(self.L):
-            p = f"transformer.h.{l}."
-            x = self._ln(h, p + "ln_1")
-            qkv = self._gemm(x, p + "attn.c_attn", R, 3 * E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+        def self_attn(l, qkv):
             a = torch.empty(R, E, dtype=torch.bfloat16, device=dev)
             for b, r in enumerate(rows):
                 ops.attn_fwd(qkv[r, :E], qkv[r, E:2 * E], qkv[r, 2 * E:], 1, H, lens[b], lens[b], True, o=a[r])
                 self.kv[l][slots[b], :lens[b]].copy_(qkv[r, E:])
-            self._gemm(a, p + "attn.c_proj", R, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
-            ckv = self._gemm(cap, p + "crossattention.c_attn", Rc, 2 * E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
-            for b, cr in enumerate(crows):
-                self.xkv[l][slots[b], :clens[b]].copy_(ckv[cr])
-            x = self._ln(h, p + "ln_cross_attn")
-            q = self._gemm(x, p + "crossattention.q_attn", R, E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+            return a
+
+        def cross_attn(l, q):   # the captions' K | V of this layer, to the slots and under the queries
+            ckv = self._gemm(cap, f"transformer.h.{l}.crossattention.c_attn", Rc, 2 * E, E, out_dtype=torch.bfloat16,
+                             epilogue=L.EPI_BIAS)
             a = torch.empty(R, E, dtype=torch.bfloat16, device=dev)
             for b, (r, cr) in enumerate(zip(rows, crows)):
+                self.xkv[l][slots[b], :clens[b]].copy_(ckv[cr])
                 ops.attn_fwd(q[r], ckv[cr, :E], ckv[cr, E:], 1, H, lens[b], clens[b], False, o=a[r])
-            self._gemm(a, p + "crossattention.c_proj", R, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
-            self._mlp(p, h, R)
+            return a
+
+        for l in range(self.L):
+            self._block(l, h, R, self_attn, cross_attn)
         last = torch.tensor([q0[b] + lens[b] - 1 for b in range(n_seq)], device=dev)
         sl = torch.tensor(slots, device=dev)
         self._logits[sl] = self._head(h.index_select(0, last))
@@ -919,10 +910,7 @@ class ContinuousGenerator:
         R = sum(lens)
         h = ops.embed_rows(ids, tt, pos, self._f("__wte_pad"), self._f("transformer.wpe.weight"))
         rows = [slice(q0[b], q0[b] + lens[b]) for b in range(n_seq)]
-        for l in range(self.L):
-            p = f"transformer.h.{l}."
-            x = self._ln(h, p + "ln_1")
-            qkv = self._gemm(x, p + "attn.c_attn", R, 3 * E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+        def self_attn(l, qkv):
             a = torch.empty(R, E, dtype=torch.bfloat16, device=dev)
             for b, r in enumerate(rows):
                 n_all = past[b] + lens[b]
@@ -932,15 +920,17 @@ class ContinuousGenerator:
                 kvb = self.kv[l][slots[b], :n_all]
                 ob, _ = ops.attn_fwd(qf, kvb[:, :E], kvb[:, E:], 1, H, n_all, n_all, True)
                 a[r] = ob[past[b]:]
-            self._gemm(a, p + "attn.c_proj", R, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
-            x = self._ln(h, p + "ln_cross_attn")
-            q = self._gemm(x, p + "crossattention.q_attn", R, E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
+            return a
+
+        def cross_attn(l, q):
             a = torch.empty(R, E, dtype=torch.bfloat16, device=dev)
             for b, r in enumerate(rows):
                 kvb = self.xkv[l][slots[b], :clens[b]]
                 ops.attn_fwd(q[r], kvb[:, :E], kvb[:, E:], 1, H, lens[b], clens[b], False, o=a[r])
-            self._gemm(a, p + "crossattention.c_proj", R, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
-            self._mlp(p, h, R)
+            return a
+
+        for l in range(self.L):
+            self._block(l, h, R, self_attn, cross_attn)
         last = torch.tensor([q0[b] + lens[b] - 1 for b in range(n_seq)], device=dev)
         sl = torch.tensor(slots, device=dev)
         self._logits[sl] = self._head(h.index_select(0, last))
@@ -966,7 +956,7 @@ class ContinuousGenerator:
         """Append one token per slot (int64 [max_batch] on the device; what an idle or finished slot gets does not
         matter) and return the logits [max_batch, V].  A live row's length and draw counter advance by one, and it
         finishes when it reaches the bound of its admission."""
-        B, E = self.max_batch, self.E
+        B = self.max_batch
         tokens, token_types = tokens.reshape(-1), token_types.reshape(-1)
         if tokens.numel() != B or token_types.numel() != B:
             raise ValueError(f"step takes one token and one token type per slot ({B})")
@@ -977,22 +967,8 @@ class ContinuousGenerator:
             L.call("ergm_decode_step_slots", self._plan, C.c_void_p(tokens.data_ptr()),
                    C.c_void_p(token_types.data_ptr()), self._stream())
             return self.logits
-        lens, cap_lens = self.lens, self.cap_lens
-        h = ops.embed_rows(tokens, token_types, lens, self._f("__wte_pad"), self._f("transformer.wpe.weight"))
-        for l in range(self.L):
-            p = f"transformer.h.{l}."
-            x = self._ln(h, p + "ln_1")
-            qkv = self._gemm(x, p + "attn.c_attn", B, 3 * E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
-            cache = self.kv[l]
-            a = ops.attn_decode(qkv, cache[:, :, :E], cache[:, :, E:], lens, True, ws=self._ws)
-            self._gemm(a, p + "attn.c_proj", B, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
-            x = self._ln(h, p + "ln_cross_attn")
-            q = self._gemm(x, p + "crossattention.q_attn", B, E, E, out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS)
-            xkv = self.xkv[l]
-            a = ops.attn_decode(q, xkv[:, :, :E], xkv[:, :, E:], cap_lens, False, ws=self._ws)
-            self._gemm(a, p + "crossattention.c_proj", B, E, E, out=h, epilogue=L.EPI_BIAS_RESID, aux=h)
-            self._mlp(p, h, B)
-        self._logits.copy_(self._head(h))
+        lens = self.lens
+        self._logits.copy_(self._step_rows(tokens, token_types, lens, self.cap_lens, self.kv, self.xkv))
         live = self.finished == 0
         lens.add_(live.to(torch.int32))
         self.row_steps.add_(live.to(torch.int32))

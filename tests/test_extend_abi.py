@@ -69,11 +69,11 @@ def test_extend_refusals_without_a_gpu():
         lib.ergm_decode_destroy(plan)
 
 
-def _gemm_kernels(M, N, K, nk=False, c_dtype=L.BF16, epi=L.EPI_BIAS):
+def _gemm_kernels(M, N, K, nk=False, c_dtype=L.BF16, epi=L.EPI_BIAS, ldb=None):
     """1, or 2 when ergm_gemm_plan splits K (the GEMM and its reduction), for the executor's descriptor."""
     keep, p = CA._buf()
-    g = L.GemmDesc(M=M, N=N, K=K, lda=K, ldb=K if nk else N, ldc=N, a_layout=L.MK, b_layout=L.NK if nk else L.KN,
-                   c_dtype=c_dtype, epilogue=epi, alpha=1.0)
+    g = L.GemmDesc(M=M, N=N, K=K, lda=K, ldb=ldb or (K if nk else N), ldc=N, a_layout=L.MK,
+                   b_layout=L.NK if nk else L.KN, c_dtype=c_dtype, epilogue=epi, alpha=1.0)
     if epi != L.EPI_NONE:
         g.bias = p
     if epi == L.EPI_BIAS_RESID:
@@ -85,14 +85,75 @@ def _gemm_kernels(M, N, K, nk=False, c_dtype=L.BF16, epi=L.EPI_BIAS):
     return 2 if split.value > 1 else 1
 
 
+def _block_gemms(R, E, F):
+    """The six GEMMs of a block over R rows, in every mode: qkv, the cross query, c_fc and the three projections."""
+    return (_gemm_kernels(R, 3 * E, E) + _gemm_kernels(R, E, E) + _gemm_kernels(R, F, E, epi=L.EPI_BIAS_GELU)
+            + 2 * _gemm_kernels(R, E, E, c_dtype=L.F32, epi=L.EPI_BIAS_RESID)
+            + _gemm_kernels(R, E, F, c_dtype=L.F32, epi=L.EPI_BIAS_RESID))
+
+
+def _head_gemm(rows, E, Vp):
+    return _gemm_kernels(rows, Vp, E, nk=True, c_dtype=L.F32, epi=L.EPI_NONE)
+
+
 def extend_kernels(R, n_seq, E, F, Vp, n_layer):
     """The launch sequence of ergm_decode_extend, counted by hand: the embedding; per block 3 LayerNorms, the row
     scatter, the two attentions and 6 GEMMs; the gather of the last rows, ln_f, the head, the logits scatter and the
     slot state."""
-    block = (6 + _gemm_kernels(R, 3 * E, E) + _gemm_kernels(R, E, E) + _gemm_kernels(R, F, E, epi=L.EPI_BIAS_GELU)
-             + 2 * _gemm_kernels(R, E, E, c_dtype=L.F32, epi=L.EPI_BIAS_RESID)
-             + _gemm_kernels(R, E, F, c_dtype=L.F32, epi=L.EPI_BIAS_RESID))
-    return 1 + n_layer * block + 4 + _gemm_kernels(n_seq, Vp, E, nk=True, c_dtype=L.F32, epi=L.EPI_NONE)
+    return 1 + n_layer * (6 + _block_gemms(R, E, F)) + 4 + _head_gemm(n_seq, E, Vp)
+
+
+def admit_kernels(R, Rc, n_seq, E, F, Vp, n_layer):
+    """The launch sequence of ergm_decode_admit, counted by hand: the packed embedding; per block 3 LayerNorms, the two
+    ragged attentions, the two row scatters, the block's 6 GEMMs and the caption K | V GEMM over layer l's columns of
+    the stacked weight (ldb = L·2E); the gather of the last rows, ln_f, the head, the logits scatter, the slot state."""
+    cap = _gemm_kernels(Rc, 2 * E, E, ldb=n_layer * 2 * E)
+    return 1 + n_layer * (7 + _block_gemms(R, E, F) + cap) + 4 + _head_gemm(n_seq, E, Vp)
+
+
+def _attn_decode_kernels(B, H, rows):
+    """Launches of one ergm_attn_decode call with splits = 0, from the header's description: the partials of `splits`
+    chunks go through a workspace of B·H·splits·66 floats, ergm_attn_decode_workspace_size covers the automatic choice,
+    and more than one split adds the merge.  Where the query has room for one split only, the choice is 1 and the call
+    is one launch.  Where it has room for more the header does not fix the choice ("1 when B*H fills the chip"):
+    None, and the caller stays with a bound."""
+    room = L.load().ergm_attn_decode_workspace_size(B, H, rows) // (B * H * 66 * 4)
+    return 1 if room == 1 else None
+
+
+def step_kernels(B, engine, E, F, Vp, n_layer, H, max_len, cap_rows):
+    """The launch sequence of one decode step over B rows, counted by hand: the embedding; per block the two decode
+    attentions and, on engine 0, 3 LayerNorms and 6 GEMMs, on engine 1 one ergm_linear_rows in the place of each
+    LayerNorm + GEMM pair and of each projection (6 launches); ln_f, the head GEMM (both engines) and the length
+    update.  None where the attention's split choice cannot be told from the header."""
+    attn = [_attn_decode_kernels(B, H, max_len), _attn_decode_kernels(B, H, cap_rows)]
+    if None in attn:
+        return None
+    block = sum(attn) + (3 + _block_gemms(B, E, F) if engine == 0 else 6)
+    return 1 + n_layer * block + 1 + _head_gemm(B, E, Vp) + 1
+
+
+def test_admit_and_step_launch_counts_are_exact():
+    """The dry walks against the hand counts, at the tiny dims: the admission at three row counts that take different
+    GEMM configurations, for 1 and 3 sequences; the step unbound (all max_batch rows, cap_max caption rows) and bound
+    to one sequence, on both engines."""
+    lib = L.load()
+    plan, keep, p = CA._plan()
+    E, F, Vp, n_layer, H = (TINY[k] for k in ("n_embd", "n_inner", "vocab_pad", "n_layer", "n_head"))
+    try:
+        for rows, cap_rows in ((3, 3), (30, 22), (100, 64)):
+            for n_seq in (1, 3):
+                assert (lib.ergm_decode_admit_launches(plan, n_seq, rows, cap_rows)
+                        == admit_kernels(rows, cap_rows, n_seq, E, F, Vp, n_layer)), (rows, cap_rows, n_seq)
+        ptrs = (C.c_void_p * n_layer)(*[p.value] * n_layer)
+        for B, Sc in ((TINY["max_batch"], TINY["cap_max"]), (1, 4)):
+            if B == 1:
+                assert lib.ergm_decode_bind(plan, 1, 8, ptrs, ptrs, Sc, p, p, p, p) == L.ERGM_OK
+            for engine in (0, 1):
+                want = step_kernels(B, engine, E, F, Vp, n_layer, H, TINY["max_len"], Sc)
+                assert want is not None and lib.ergm_decode_launches(plan, engine) == want, (B, engine)
+    finally:
+        lib.ergm_decode_destroy(plan)
 
 
 def test_extend_launch_count_is_a_dry_walk():
