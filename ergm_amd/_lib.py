@@ -83,6 +83,12 @@ class DecodeDims(C.Structure):
                 ("max_len", C.c_int), ("cap_max", C.c_int), ("eps", C.c_float)]
 
 
+class SampleCtl(C.Structure):
+    """ergm_sample_ctl (ergm_hip.h): device arrays [B] of per-row sampling controls, None for a default."""
+    _fields_ = [("top_p", C.c_void_p), ("temperature", C.c_void_p), ("rep_penalty", C.c_void_p), ("top_k", C.c_void_p),
+                ("min_step", C.c_void_p), ("seen", C.c_void_p), ("ld_seen", C.c_int)]
+
+
 vp, i32, i64, f32, f64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 _SIGS = {
     "ergm_version": (i32, []),
@@ -111,6 +117,8 @@ _SIGS = {
     "ergm_embed_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ergm_topp_sample": (i32, [vp, i32, i32, i32, f32, C.c_uint64, C.c_uint32, vp, i64, vp, vp, vp, vp]),
     "ergm_topp_sample_rows": (i32, [vp, i32, i32, i32, f32, C.c_uint64, vp, vp, vp, i64, vp, vp, vp, vp]),
+    "ergm_sample_rows": (i32, [vp, i32, i32, i32, f32, C.POINTER(SampleCtl), C.c_uint64, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
+    "ergm_sample_mark": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
     "ergm_rows_to_slots": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp, i64, i64, i32, i32, i32, vp]),
     "ergm_rows_to_slots_at": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, i64, i64, i32, i32, i32, vp]),
     "ergm_embed_packed": (i32, [vp] * 12 + [i32] * 5 + [vp, vp, i32, i32, i32, i32, vp]),
@@ -134,6 +142,7 @@ _SIGS = {
     "ergm_decode_extend_launches": (i32, [vp, i32, i32]),
     "ergm_decode_step_slots": (i32, [vp, vp, vp, vp]),
     "ergm_decode_run_slots": (i32, [vp, i32, f32, C.c_uint64, i64, i64, vp, vp]),
+    "ergm_decode_run_slots_sampled": (i32, [vp, i32, f32, C.POINTER(SampleCtl), C.c_uint64, i64, i64, vp, vp, vp]),
     "ergm_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "ergm_layernorm_bwd_workspace_size": (sz, [i32, i32]),
     "ergm_layernorm_bwd": (i32, [vp] * 10 + [sz, i32, i32, vp, vp]),

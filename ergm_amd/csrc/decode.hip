@@ -1,6 +1,7 @@
 // Batched KV-cache generation for gfx950: decode attention of one query per sequence over a ragged cache,
 // the embedding of one token per sequence at its own position, and nucleus (top-p) sampling of a batch of
-// logit rows without a sort (ergm_hip.h: ergm_attn_decode, ergm_embed_rows, ergm_topp_sample).
+// logit rows without a sort (ergm_hip.h: ergm_attn_decode, ergm_embed_rows, ergm_topp_sample, and ergm_sample_rows
+// with its per-row sampling controls).
 //
 // Decode attention is a GEMV over the cache: VALU work behind 16-byte loads, no MFMA.  A workgroup of 4 waves
 // owns one (split, head, sequence).  8 lanes share a key row (8 bf16 of the 64-wide head each), so one wave
@@ -375,6 +376,257 @@ __global__ __launch_bounds__(TP_THREADS) void topp_sample_kernel(const float* __
     }
 }
 
+// ---- sampling with per-row controls (ergm_sample_rows) ---------------------------------------------------
+// NaN, infinite or <= 0 acts as 1
+__device__ __forceinline__ float sm_scale(const float* p, int b) {
+    const float v = p ? p[b] : 1.f;
+    return (v > 0.f && v < INFINITY) ? v : 1.f;
+}
+// the repetition penalty on the logit of a token the row has seen
+__device__ __forceinline__ float sm_penalty(float x, float rep) { return x < 0.f ? x * rep : __fdiv_rn(x, rep); }
+
+struct SmShared {
+    TpShared tp;
+    float mx;
+};
+
+// topp_sample_kernel with the controls of ergm_sample_ctl.  The penalty, the eos mask and the temperature act on the
+// registers right behind the load, so the passes below see what the old kernel sees.  The threshold search runs once more, ahead of
+// the mass search and with the packed count as its criterion, for the rows that ask for top-k (uniform over the
+// workgroup); its result is a few uniform values carried across the mass search.
+template <int NPT>
+__global__ __launch_bounds__(TP_THREADS) void sample_rows_kernel(const float* __restrict__ logits, int ldl, int V, float top_p,
+                                                                 ergm_sample_ctl ctl, uint32_t seed_lo, uint32_t seed_hi,
+                                                                 const uint32_t* __restrict__ row_ids,
+                                                                 const uint32_t* __restrict__ row_steps, uint8_t* finished,
+                                                                 int64_t eos_id, int64_t* __restrict__ tokens,
+                                                                 int* __restrict__ kept, float* __restrict__ kept_mass,
+                                                                 float* __restrict__ logprob) {
+    __shared__ SmShared smx;
+    TpShared& sm = smx.tp;
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (finished && finished[b]) {  // uniform over the workgroup
+        if (t == 0) {
+            tokens[b] = eos_id;
+            if (kept) kept[b] = 0;
+            if (kept_mass) kept_mass[b] = 0.f;
+            if (logprob) logprob[b] = 0.f;
+        }
+        return;
+    }
+    const int per = (V + TP_THREADS - 1) / TP_THREADS;
+    const int i0 = t * per;
+    const int nv = max(0, min(per, V - i0));  // valid tokens of this thread: j < nv
+    const float* row = logits + (size_t)b * ldl;
+    uint32_t* seen = ctl.seen ? ctl.seen + (size_t)b * ctl.ld_seen : nullptr;
+    const uint32_t cstep = row_steps[b];
+    float e[NPT];
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) e[j] = j < nv ? row[i0 + j] : -INFINITY;
+    // Steps 1 to 3 of the rule, each a pass of its own over the registers, taken only by the rows that ask for it:
+    // the penalty's and the temperature's conditions are uniform over the workgroup (a factor of 1 changes no bit, so
+    // skipping it is exact), the eos mask is the business of the one thread that holds eos.
+    const float rep = sm_scale(ctl.rep_penalty, b);
+    if (seen && rep != 1.f) {
+        uint32_t word = 0;
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) {
+            const int idx = i0 + j;
+            if (j < nv) {
+                if (j == 0 || (idx & 31) == 0) word = seen[idx >> 5];  // one read per 32 tokens
+                if ((word >> (idx & 31)) & 1u) e[j] = sm_penalty(e[j], rep);
+            }
+        }
+    }
+    // while the row is below its minimum length eos is a slot that holds no token, as a NaN logit is: no mass, never
+    // counted
+    if (ctl.min_step && cstep < ctl.min_step[b] && eos_id >= i0 && eos_id < i0 + nv) {
+        const int eos_j = (int)eos_id - i0;
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) e[j] = j == eos_j ? __builtin_nanf("") : e[j];
+    }
+    const float temp = sm_scale(ctl.temperature, b);
+    if (temp != 1.f) {
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) e[j] = __fdiv_rn(e[j], temp);
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) mx = fmaxf(mx, e[j]);
+    mx = wave_max(mx);
+    if ((t & 63) == 0) sm.red[t >> 6] = mx;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < TP_THREADS / 64; ++w) mx = fmaxf(mx, sm.red[w]);
+    if (t == 0) smx.mx = mx;
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const float x = expf(e[j] - mx);
+        e[j] = (j < nv && x >= 0.f) ? x : -1.f;
+        const unsigned long long q = tp_q(e[j]);
+        mine += q ? (1ull << TP_CNT_SHIFT) | q : 0ull;  // count << 47 | mass of the tokens with mass
+    }
+    unsigned long long Sn;
+    tp_scan(mine, sm.scan, Sn);
+    const unsigned long long S = Sn & TP_MASS_MASK;
+    const float tp = ctl.top_p ? ctl.top_p[b] : top_p;
+    const int k_raw = ctl.top_k ? ctl.top_k[b] : 0;
+    // top-k is on for 1 <= k < the number of tokens with mass
+    const unsigned k = (k_raw >= 1 && (unsigned long long)k_raw < (Sn >> TP_CNT_SHIFT)) ? (unsigned)k_raw : 0u;
+    // the result of the top-k search (k != 0): the smallest value that remains, what lies above it, its ties that remain
+    unsigned k_key = 0, k_ties = 0;
+    unsigned long long k_above = 0;
+    // T: the largest mass of the ranks before a kept token, over the mass S_k that remains under top-k
+    unsigned long long T = 0;
+    unsigned prefix = 0;
+    unsigned long long above = 0, in_bin = 0;
+#pragma unroll 1
+    for (int pass = k ? 0 : 1; pass < 2; ++pass) {
+        // pass 0 looks for the smallest value with fewer than k tokens above it, pass 1 for the smallest with at most
+        // T of mass above it: the same walk over the packed words, by count or by mass
+        const bool by_count = pass == 0;
+        if (!by_count) {
+            const unsigned long long qk = tp_q(__uint_as_float(k_key));
+            const unsigned long long Sk = k ? (k_above & TP_MASS_MASK) + k_ties * qk : S;
+            T = tp >= 1.f ? Sk : (tp > 0.f ? (unsigned long long)((double)tp * (double)Sk) : 0ull);
+            T = min(T, Sk);
+        }
+        const unsigned long long lim = by_count ? (unsigned long long)(k - 1) : T;
+        prefix = 0, above = 0, in_bin = 0;
+#pragma unroll 1
+        for (int level = 0; level < 3; ++level) {
+            const int shift = level == 0 ? 20 : (level == 1 ? 9 : 0);
+            const int bits = level == 2 ? 9 : 11;
+            sm.hist[t] = 0;
+            sm.hist[t + TP_THREADS] = 0;
+            if (t == 0) sm.sel = TP_BINS;
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < NPT; ++j) {
+                const float ej = tp_use(e[j]);
+                const unsigned key = __float_as_uint(ej);
+                if (ej >= 0.f && (level == 0 || (key >> (shift + bits)) == prefix))
+                    atomicAdd(&sm.hist[(key >> shift) & ((1u << bits) - 1)], (1ull << TP_CNT_SHIFT) | tp_q(ej));
+            }
+            __syncthreads();
+            const int bh = TP_BINS - 1 - 2 * t, bl = bh - 1;
+            const unsigned long long hh = sm.hist[bh], hl = sm.hist[bl];
+            unsigned long long tot;
+            const unsigned long long ah = above + tp_scan(hh + hl, sm.scan, tot), al = ah + hh;
+            const unsigned long long ch = by_count ? ah >> TP_CNT_SHIFT : ah & TP_MASS_MASK;
+            const unsigned long long cl = by_count ? al >> TP_CNT_SHIFT : al & TP_MASS_MASK;
+            if (hl && cl <= lim) atomicMin(&sm.sel, bl);
+            else if (hh && ch <= lim) atomicMin(&sm.sel, bh);
+            __syncthreads();
+            const int sel = sm.sel;
+            if (sel == bh || sel == bl) {
+                sm.pick[0] = sel == bh ? ah : al;
+                sm.pick[1] = sel == bh ? hh : hl;
+            }
+            __syncthreads();
+            above = sm.pick[0];
+            in_bin = sm.pick[1];
+            prefix = (prefix << bits) | (unsigned)sel;
+            __syncthreads();
+        }
+        if (by_count) {  // of the ties at the smallest remaining value, the k - (tokens above) lowest ids remain
+            k_key = prefix, k_above = above;
+            k_ties = min((unsigned)(in_bin >> TP_CNT_SHIFT), k - (unsigned)(above >> TP_CNT_SHIFT));
+        }
+    }
+    // prefix = the bit pattern of the smallest kept value v; `in_bin` counts its ties, kept in token order while
+    // the mass before each stays <= T
+    unsigned vkey = prefix;
+    const unsigned long long G = above & TP_MASS_MASK, qv = tp_q(__uint_as_float(vkey));
+    const unsigned ties = (unsigned)(in_bin >> TP_CNT_SHIFT);
+    unsigned keep_ties = qv == 0 ? ties : (unsigned)min((unsigned long long)ties, (T - G) / qv + 1);
+    // top-p reaches past the ranks that remain under top-k (T = S_k): the top-k cut is the kept set
+    if (k && (unsigned)(above >> TP_CNT_SHIFT) + keep_ties > k) vkey = k_key, above = k_above, keep_ties = k_ties;
+    unsigned long long c_eq = 0;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) c_eq += __float_as_uint(tp_use(e[j])) == vkey ? 1u : 0u;
+    unsigned long long tot;
+    unsigned rank = (unsigned)tp_scan(c_eq, sm.scan, tot);  // ties in lower token ids
+    unsigned keepbits_lo = 0, keepbits_hi = 0;
+    mine = 0;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const float ej = tp_use(e[j]);
+        const unsigned key = __float_as_uint(ej);
+        bool kp = ej >= 0.f && key > vkey;
+        if (key == vkey) kp = rank++ < keep_ties;
+        if (kp) {
+            mine += tp_q(ej);
+            if (j < 32) keepbits_lo |= 1u << j;
+            else keepbits_hi |= 1u << (j - 32);
+        }
+    }
+    unsigned long long K;
+    unsigned long long run = tp_scan(mine, sm.scan, K);
+    // the draw: first kept token, in token order, whose running sum reaches u·K
+    const uint4 r = philox4x32_10(make_uint4(row_ids[b], 0u, 0xE5A3u, cstep), seed_lo, seed_hi);
+    const double u = ((double)r.x + 0.5) * (1.0 / 4294967296.0);
+    unsigned long long target = (unsigned long long)ceil(u * (double)K);
+    target = max(1ull, min(target, K));
+    if (t == 0) sm.sel = V - 1;
+    __syncthreads();
+    bool found = false;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const bool kp = j < 32 ? (keepbits_lo >> j) & 1u : (keepbits_hi >> (j - 32)) & 1u;
+        if (kp) {
+            run += tp_q(tp_use(e[j]));
+            if (!found && run >= target) {
+                found = true;
+                atomicMin(&sm.sel, i0 + j);
+            }
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        const int tok = sm.sel;  // in [0, V): V - 1 or a valid token of some thread
+        tokens[b] = tok;
+        if (kept) kept[b] = (int)(above >> TP_CNT_SHIFT) + (int)keep_ties;
+        if (kept_mass) kept_mass[b] = (float)((double)K / (double)S);
+        if (finished && tok == eos_id) finished[b] = 1;
+        if (logprob) {  // the token's processed logit once more, from the row and the bitmap as the load saw them
+            float x = row[tok];
+            if (seen && (seen[tok >> 5] >> (tok & 31)) & 1u) x = sm_penalty(x, sm_scale(ctl.rep_penalty, b));
+            x = __fdiv_rn(x, sm_scale(ctl.temperature, b));
+            logprob[b] = (float)((double)(x - smx.mx) - log((double)S * (1.0 / 1073741824.0)));
+        }
+        if (seen) seen[tok >> 5] |= 1u << (tok & 31);  // this workgroup alone writes the row
+    }
+}
+
+// One workgroup per sequence: clear the slot's bitmap row, barrier, set the bits of the sequence's ids, and the
+// turn's minimum length.  Everything read from the device arrays is checked before an address is formed.
+__global__ __launch_bounds__(256) void sample_mark_kernel(const int64_t* __restrict__ ids, int total,
+                                                          const int* __restrict__ slot, const int* __restrict__ start,
+                                                          const int* __restrict__ len, const int* __restrict__ reset,
+                                                          const int* __restrict__ min_new, int V, int n_slots,
+                                                          uint32_t* __restrict__ seen, int ld_seen,
+                                                          const uint32_t* __restrict__ row_steps,
+                                                          uint32_t* __restrict__ min_step) {
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int sl = slot[b];
+    if (sl < 0 || sl >= n_slots) return;  // uniform over the workgroup
+    if (seen) {
+        uint32_t* row = seen + (size_t)sl * ld_seen;
+        if (reset && reset[b])
+            for (int w = t; w < (V + 31) / 32; w += 256) row[w] = 0u;
+        __syncthreads();
+        const int n = max(0, min(len[b], total));
+        const int s0 = max(0, min(start[b], total - n));
+        for (int i = t; i < n; i += 256) {
+            const int64_t id = ids[s0 + i];
+            if (id >= 0 && id < V) atomicOr(&row[id >> 5], 1u << (id & 31));
+        }
+    }
+    if (t == 0 && min_step) min_step[sl] = row_steps[sl] + (uint32_t)max(min_new ? min_new[b] : 0, 0);
+}
+
 // ---- the decode executor's integer helpers (decode_exec.cpp) -------------------------------------------
 // lens[b] += !finished[b]: the sequences that have not drawn eos advance by the token just appended
 __global__ void lens_advance_kernel(int* __restrict__ lens, const uint8_t* __restrict__ finished, int B) {
@@ -573,6 +825,47 @@ extern "C" int ergm_topp_sample_rows(const float* logits, int ldl, int B, int V,
     ERGM_CHECK_ARG(row_ids && row_steps, "topp_sample_rows: null row_ids or row_steps");
     return topp_launch("topp_sample_rows", logits, ldl, B, V, top_p, seed, 0u, row_ids, row_steps, finished, eos_id, tokens,
                        kept, kept_mass, stream);
+}
+
+extern "C" int ergm_sample_rows(const float* logits, int ldl, int B, int V, float top_p, const ergm_sample_ctl* ctl,
+                                uint64_t seed, const uint32_t* row_ids, const uint32_t* row_steps, void* finished,
+                                int64_t eos_id, int64_t* tokens, int* kept, float* kept_mass, float* logprob, void* stream) {
+    ERGM_CHECK_ARG(logits && tokens, "sample_rows: null logits or tokens");
+    ERGM_CHECK_ARG(row_ids && row_steps, "sample_rows: null row_ids or row_steps");
+    ERGM_CHECK_ARG(B > 0 && ldl >= V, "sample_rows: bad shape B %d V %d ldl %d", B, V, ldl);
+    ERGM_CHECK_ARG(V > 0 && V <= 52 * TP_THREADS, "sample_rows: V %d outside [1, %d]", V, 52 * TP_THREADS);
+    ERGM_CHECK_ARG(top_p == top_p, "sample_rows: top_p is NaN");
+    ergm_sample_ctl c{};
+    if (ctl) c = *ctl;
+    ERGM_CHECK_ARG(!c.seen || c.ld_seen >= cdiv(V, 32), "sample_rows: ld_seen %d < the %d words of a row's bitmap", c.ld_seen,
+                   cdiv(V, 32));
+    hipStream_t s = as_stream(stream);
+    auto* fin = reinterpret_cast<uint8_t*>(finished);
+    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
+    const int per = cdiv(V, TP_THREADS);
+#define ERGM_SAMPLE(NPT)                                                                                               \
+    ERGM_LAUNCH(sample_rows_kernel<NPT>, dim3(B), dim3(TP_THREADS), 0, s, logits, ldl, V, top_p, c, lo, hi, row_ids, \
+                row_steps, fin, eos_id, tokens, kept, kept_mass, logprob)
+    if (per <= 4) ERGM_SAMPLE(4);
+    else if (per <= 16) ERGM_SAMPLE(16);
+    else ERGM_SAMPLE(52);
+#undef ERGM_SAMPLE
+    return check_launch("sample_rows");
+}
+
+extern "C" int ergm_sample_mark(const int64_t* ids, int total, const int* slot, const int* start, const int* len,
+                                const int* reset, const int* min_new, int n_seq, int V, int n_slots, uint32_t* seen,
+                                int ld_seen, const uint32_t* row_steps, uint32_t* min_step, void* stream) {
+    ERGM_CHECK_ARG(ids && slot && start && len, "sample_mark: null argument");
+    ERGM_CHECK_ARG(seen || min_step, "sample_mark: neither a bitmap nor min_step to write");
+    ERGM_CHECK_ARG((min_step == nullptr) == (row_steps == nullptr), "sample_mark: min_step and row_steps go together");
+    ERGM_CHECK_ARG(n_seq > 0 && n_seq <= 65535 && total > 0 && V > 0 && n_slots > 0,
+                   "sample_mark: bad shape n_seq %d total %d V %d n_slots %d", n_seq, total, V, n_slots);
+    ERGM_CHECK_ARG(!seen || ld_seen >= cdiv(V, 32), "sample_mark: ld_seen %d < the %d words of a row's bitmap", ld_seen,
+                   cdiv(V, 32));
+    ERGM_LAUNCH(sample_mark_kernel, dim3(n_seq), dim3(256), 0, as_stream(stream), ids, total, slot, start, len, reset, min_new,
+                V, n_slots, seen, ld_seen, row_steps, min_step);
+    return check_launch("sample_mark");
 }
 
 namespace {

@@ -728,6 +728,27 @@ extern "C" int ergm_decode_run_slots(ergm_decode_plan* P, int n, float top_p, ui
     return ERGM_OK;
 }
 
+extern "C" int ergm_decode_run_slots_sampled(ergm_decode_plan* P, int n, float top_p, const ergm_sample_ctl* ctl, uint64_t seed,
+                                             int64_t eos_id, int64_t sp2_id, int64_t* tokens_out, float* logprobs_out,
+                                             void* stream) {
+    ERGM_TRY(slots_ready(P, "decode_run_slots_sampled"));
+    ERGM_CHECK_ARG(n >= 1, "decode_run_slots_sampled: n %d < 1", n);
+    ERGM_CHECK_ARG(tokens_out, "decode_run_slots_sampled: null tokens_out");
+    ERGM_CHECK_ARG(top_p == top_p, "decode_run_slots_sampled: top_p is NaN");
+    hipStream_t s = as_stream(stream);
+    const int B = P->d.max_batch;
+    ERGM_TRY(decode_fill_i64(P->tt, sp2_id, B, s));
+    for (int i = 0; i < n; ++i) {
+        int64_t* tok = tokens_out + (size_t)i * B;
+        ERGM_TRY(ergm_sample_rows(P->logits, P->d.vocab_pad, B, P->d.vocab, top_p, ctl, seed, P->row_ids, P->row_steps,
+                                  P->finished, eos_id, tok, nullptr, nullptr, logprobs_out ? logprobs_out + (size_t)i * B : nullptr,
+                                  s));
+        Walk w{false, "decode_step", s};
+        ERGM_TRY(walk(P, w, P->engine, B, tok, P->tt));
+    }
+    return ERGM_OK;
+}
+
 extern "C" int ergm_decode_launches(const ergm_decode_plan* P, int engine) {
     ERGM_CHECK_ARG(P && engine >= 0 && engine < kEngines, "decode_launches: bad plan or engine %d", engine);
     Walk w{true, "decode_launches"};

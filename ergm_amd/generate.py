@@ -28,6 +28,8 @@ host-only policy.
 from __future__ import annotations
 
 import ctypes as C
+import math
+from dataclasses import dataclass, replace
 from typing import List, Optional
 
 import torch
@@ -465,15 +467,48 @@ class BatchedGenerator:
 NO_REQUEST = -1
 
 
-class _Request:
-    __slots__ = ("id", "n", "c", "max_new", "payload", "tokens", "slot", "keep", "past")
+@dataclass(frozen=True)
+class SamplingParams:
+    """What one request asks of the sampler (ergm_sample_rows applies them in this order): ``repetition_penalty`` over
+    the tokens its cache holds and the ones it drew, no eos before ``min_new_tokens`` tokens of the turn,
+    ``temperature``, ``top_k`` (0: off; 1: greedy), then ``top_p`` over what top-k left (None: the run's).
+    ``logprobs``: keep the log-probability of every returned token (``ContinuousGenerator.token_logprobs``)."""
+    top_p: Optional[float] = None
+    temperature: float = 1.0
+    top_k: int = 0
+    repetition_penalty: float = 1.0
+    min_new_tokens: int = 0
+    logprobs: bool = False
 
-    def __init__(self, rid: int, n: int, c: int, max_new: int, payload, keep: bool = False, past: int = 0):
+    def __post_init__(self):
+        for name in ("top_p", "temperature", "repetition_penalty"):
+            v = getattr(self, name)
+            if v is None and name == "top_p":
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f"{name} {v!r} is not a finite number")
+        if self.temperature <= 0 or self.repetition_penalty <= 0:
+            raise ValueError("temperature and repetition_penalty must be positive")
+        for name in ("top_k", "min_new_tokens"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 31:
+                raise ValueError(f"{name} {v!r} is not an integer in [0, 2^31)")
+
+    def check_bound(self, max_new_tokens: int) -> None:
+        if self.min_new_tokens > max_new_tokens:
+            raise ValueError(f"min_new_tokens {self.min_new_tokens} > max_new_tokens {max_new_tokens}")
+
+
+class _Request:
+    __slots__ = ("id", "n", "c", "max_new", "payload", "tokens", "slot", "keep", "past", "sampling")
+
+    def __init__(self, rid: int, n: int, c: int, max_new: int, payload, keep: bool = False, past: int = 0, sampling=None):
         self.id, self.n, self.c, self.max_new, self.payload = rid, n, c, max_new, payload
         self.tokens: List[int] = []
         self.slot = NO_REQUEST
         self.keep = keep      # park the slot when the request ends
         self.past = past      # a continuation: the rows its slot already holds (n counts the new ones)
+        self.sampling = sampling   # a SamplingParams or None, for the backend
 
 
 class SlotScheduler:
@@ -527,10 +562,11 @@ class SlotScheduler:
         self.extensions: List[List[tuple]] = []   # per extend_requests call: (request id, slot) pairs
 
     def submit(self, n: int, c: int, max_new_tokens: Optional[int] = None, request_id: Optional[int] = None,
-               payload=None, keep: bool = False) -> int:
+               payload=None, keep: bool = False, sampling=None) -> int:
         """Queue a request with a prompt of n tokens and c caption tokens; returns its id (uint32, arrival order by
-        default).  ``keep``: park the slot when the request ends, for ``extend``.  Raises ValueError when it can never
-        be served: it would not fit a cache or one admission."""
+        default).  ``keep``: park the slot when the request ends, for ``extend``.  ``sampling``: a ``SamplingParams``
+        the backend finds on the request (``.sampling``).  Raises ValueError when it can never be served: it would not
+        fit a cache or one admission, or its minimum length is above its bound."""
         if n < 1 or c < 1:
             raise ValueError("empty prompt or caption")
         if n >= self.max_len:
@@ -543,6 +579,8 @@ class SlotScheduler:
             max_new_tokens = self.max_len - n
         if not 1 <= max_new_tokens <= self.max_len - n:
             raise ValueError(f"max_new_tokens {max_new_tokens} outside [1, {self.max_len - n}] (max_len - the prompt)")
+        if sampling is not None:
+            sampling.check_bound(max_new_tokens)
         rid = self._next_id if request_id is None else request_id
         if not 0 <= rid < 2 ** 32:
             raise ValueError("request ids are uint32")
@@ -550,11 +588,11 @@ class SlotScheduler:
             raise ValueError(f"request id {rid} is already queued or running")
         self._active.add(rid)
         self._next_id = (rid + 1) % 2 ** 32 if request_id is None else self._next_id
-        self.queue.append(_Request(rid, n, c, max_new_tokens, payload, keep))
+        self.queue.append(_Request(rid, n, c, max_new_tokens, payload, keep, sampling=sampling))
         return rid
 
     def extend(self, request_id: int, n_new: int, max_new_tokens: Optional[int] = None, payload=None,
-               keep: bool = True) -> int:
+               keep: bool = True, sampling=None) -> int:
         """Queue n_new more tokens (``payload``) for a parked request and up to max_new_tokens new ones behind them
         (default: to the end of the cache); its slot stays held until the next look.  Raises ValueError when the id is
         not parked, n_new is outside [1, max_admit_tokens], or the cache has no room for the new rows and one new
@@ -577,8 +615,10 @@ class SlotScheduler:
             max_new_tokens = room
         if not 1 <= max_new_tokens <= room:
             raise ValueError(f"max_new_tokens {max_new_tokens} outside [1, {room}]")
+        if sampling is not None:
+            sampling.check_bound(max_new_tokens)
         del self.parked[request_id]
-        r = _Request(request_id, n_new, c, max_new_tokens, payload, keep, past=length)
+        r = _Request(request_id, n_new, c, max_new_tokens, payload, keep, past=length, sampling=sampling)
         r.slot = slot
         self.continuations.append(r)
         return request_id
@@ -681,12 +721,19 @@ class ContinuousGenerator:
     ``engine``: "python" (default, the yardstick) admits with the kernels the static prefill uses, sequence by sequence
     for the embedding and the attention, and drives every kernel of a step from Python; "native" / "fused" hand the
     admission (ergm_decode_admit: packed embedding, ragged attention, rows to slots) and the sample + step chunks
-    (ergm_decode_run_slots) to the library's executor."""
+    (ergm_decode_run_slots) to the library's executor.
+
+    ``controls=True``: requests carry a ``SamplingParams`` each (``submit(..., sampling=...)``).  The generator then
+    owns one value of every control per slot and the bitmap of the tokens each slot has seen, sets them behind every
+    admission and extension (ergm_sample_mark), and samples with ergm_sample_rows (ergm_decode_run_slots_sampled on the
+    executor engines): still nothing is read back inside a chunk.  With ``controls=False`` every launch is the one
+    described above."""
 
     ENGINES = BatchedGenerator.ENGINES
 
     def __init__(self, model, max_batch: int, max_len: int, cap_max: int, engine: str = "python",
-                 max_admit: Optional[int] = None, max_admit_tokens: Optional[int] = None, keep_logits: bool = False):
+                 max_admit: Optional[int] = None, max_admit_tokens: Optional[int] = None, keep_logits: bool = False,
+                 controls: bool = False):
         if engine not in self.ENGINES:
             raise ValueError(f"engine {engine!r} is not one of {sorted(self.ENGINES)}")
         cfg = model.config
@@ -717,6 +764,19 @@ class ContinuousGenerator:
         self.admit_calls = 0
         self.extend_calls = 0
         self._cap_host = [0] * mb   # the caption rows each slot was admitted with (extend's host check)
+        self.controls = controls
+        self.token_logprobs: dict = {}   # controls, logprobs=True: id -> one log-probability per token of the turn
+        if controls:
+            # rows: top_p, temperature, repetition penalty (f32 bits) and top_k, one column per slot
+            self._ctl_vals = torch.zeros(4, mb, dtype=torch.int32, device=dev)
+            self._ctl_vals[:3].view(torch.float32).fill_(1.0)
+            self.min_step = torch.zeros(mb, dtype=torch.int32, device=dev)                        # uint32 bits
+            self.seen = torch.zeros(mb, (lay.vocab + 31) // 32, dtype=torch.int32, device=dev)    # uint32 bits
+            f = lambda i: self._ctl_vals[i].view(torch.float32)
+            self._ctl = ops.sample_ctl(top_p=f(0), temperature=f(1), rep_penalty=f(2), top_k=self._ctl_vals[3],
+                                       min_step=self.min_step, seen=self.seen)
+            self._slot_sp: List[Optional[SamplingParams]] = [None] * mb   # what each slot was last given
+            self._lp_acc: List[Optional[list]] = [None] * mb              # the log-probabilities of the turn so far
         if engine != "python":
             self._create_plan()
 
@@ -765,11 +825,47 @@ class ContinuousGenerator:
         return n
 
     # ---- admission --------------------------------------------------------------------------------------
+    def _resolve(self, sampling, n_seq: int, max_new, slots=None) -> Optional[List[SamplingParams]]:
+        """The SamplingParams each of n_seq sequences runs with, checked against its bound, or None without controls.
+        An admission's None is the defaults; an extension's (``slots`` given) keeps what the slot has, with no minimum
+        length for the new turn."""
+        sampling = [None] * n_seq if sampling is None else list(sampling)
+        if len(sampling) != n_seq:
+            raise ValueError("one sampling value per sequence")
+        if not self.controls:
+            if any(s is not None for s in sampling):
+                raise ValueError("sampling parameters need ContinuousGenerator(controls=True)")
+            return None
+        for b, s in enumerate(sampling):
+            if s is None:
+                old = None if slots is None else self._slot_sp[slots[b]]
+                sampling[b] = SamplingParams() if old is None else replace(old, min_new_tokens=0)
+            sampling[b].check_bound(max_new[b])
+            if sampling[b].top_p is None and self._sampling is None:
+                raise ValueError("top_p=None takes the run's top_p: outside run / drain give the request its own")
+        return sampling
+
+    def _set_controls(self, slots, sps, ids, q0, lens, reset: bool) -> None:
+        """The slots' control values, their bitmap rows (cleared first at an admission) and their minimum length, behind
+        the admission or extension that filled them: one copy to the device, one scatter, one ergm_sample_mark."""
+        n_seq = len(slots)
+        top_p = [self._sampling[0] if sp.top_p is None else sp.top_p for sp in sps]
+        f = torch.tensor([top_p, [sp.temperature for sp in sps], [sp.repetition_penalty for sp in sps]], dtype=torch.float32)
+        i = torch.tensor([[sp.top_k for sp in sps], slots, q0, lens, [int(reset)] * n_seq,
+                          [sp.min_new_tokens for sp in sps]], dtype=torch.int32)
+        m = torch.cat([f.view(torch.int32), i]).to(self.dev)
+        self._ctl_vals[:, m[4].long()] = m[:4]
+        ops.sample_mark(ids, m[4], m[5], m[6], self.m.layout.vocab, seen=self.seen, reset=m[7], min_new=m[8],
+                        row_steps=self.row_steps, min_step=self.min_step)
+        for s, sp in zip(slots, sps):
+            self._slot_sp[s] = sp
+            self._lp_acc[s] = [] if sp.logprobs else None
+
     @torch.no_grad()
-    def admit(self, slots, prompts, max_new_tokens=None, request_ids=None) -> None:
+    def admit(self, slots, prompts, max_new_tokens=None, request_ids=None, sampling=None) -> None:
         """Prefill ``prompts`` into the free ``slots`` (low level; ``submit`` / ``run`` do this through the scheduler).
         max_new_tokens: one bound per prompt (default: to the end of the cache); request_ids: the uint32 ids the
-        draws are keyed by (default 0 .. n-1)."""
+        draws are keyed by (default 0 .. n-1); sampling (``controls=True``): one ``SamplingParams`` or None per prompt."""
         self.m.refresh_bf16()
         n_seq = len(prompts)
         slots = [int(s) for s in slots]
@@ -790,6 +886,7 @@ class ContinuousGenerator:
                                  f"max_len {self.max_len} / cap_max {self.cap_max}")
         if sum(lens) > self.sched.max_admit_tokens or n_seq > self.sched.max_admit:
             raise ValueError("more sequences or packed rows than one admission takes (max_admit, max_admit_tokens)")
+        sps = self._resolve(sampling, n_seq, max_new)
         vis, aud, has = self._features(prompts)
         q0 = [sum(lens[:b]) for b in range(n_seq)]
         c0 = [sum(clens[:b]) for b in range(n_seq)]
@@ -800,6 +897,8 @@ class ContinuousGenerator:
             self._admit_python(slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has)
         else:
             self._admit_native(slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has)
+        if sps is not None:   # behind the admission: it set row_steps, which the minimum length counts from
+            self._set_controls(slots, sps, torch.cat(ids_l).to(device=self.dev, dtype=torch.int64), q0, lens, reset=True)
 
     def _admit_python(self, slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has) -> None:
         E, H, dev, n_seq = self.E, self.H, self.dev, len(slots)
@@ -859,13 +958,15 @@ class ContinuousGenerator:
 
     # ---- extension: more than one token behind a cache that holds a past -------------------------------------
     @torch.no_grad()
-    def extend(self, slots, turns, max_new_tokens=None, past=None) -> None:
+    def extend(self, slots, turns, max_new_tokens=None, past=None, sampling=None) -> None:
         """Append the tokens of ``turns`` (one (input_ids, token_type_ids) per slot) behind what the occupied ``slots``
         hold, and leave the logits after each turn's last token in the slot (low level; ``extend_request`` / ``run``
         do this through the scheduler).  The captions, the request ids and the draw counters stay those of the
         admission.  max_new_tokens: one bound per turn (default: to the end of the cache).  past: the rows each slot
         holds; None reads them from ``lens`` (one sync).  A slot's first two positions belong to its admission (they
-        may carry the visual / audio vectors), so every past is at least 2."""
+        may carry the visual / audio vectors), so every past is at least 2.  sampling (``controls=True``): one
+        ``SamplingParams`` or None per turn; None keeps the slot's, without a minimum length.  The turn's ids join the
+        slot's bitmap: the penalty covers everything the cache holds."""
         self.m.refresh_bf16()
         n_seq = len(turns)
         slots = [int(s) for s in slots]
@@ -891,6 +992,7 @@ class ContinuousGenerator:
                                  f"does not fit max_len {self.max_len}, or its slot was never admitted")
         if sum(lens) > self.sched.max_admit_tokens or n_seq > self.sched.max_admit:
             raise ValueError("more sequences or packed rows than one extension takes (max_admit, max_admit_tokens)")
+        sps = self._resolve(sampling, n_seq, max_new, slots)
         q0 = [sum(lens[:b]) for b in range(n_seq)]
         dev = self.dev
         ids = torch.cat(ids_l).to(device=dev, dtype=torch.int64)
@@ -901,6 +1003,8 @@ class ContinuousGenerator:
             self._extend_python(slots, ids, tt, pos, lens, past, clens, q0, max_new)
         else:
             self._extend_native(slots, ids, tt, pos, lens, past, clens, q0, max_new)
+        if sps is not None:
+            self._set_controls(slots, sps, ids, q0, lens, reset=False)
 
     def _extend_python(self, slots, ids, tt, pos, lens, past, clens, q0, max_new) -> None:
         """The yardstick: the row-wise kernels over the packed rows, the K | V rows copied by torch, and the attention
@@ -977,53 +1081,90 @@ class ContinuousGenerator:
 
     @torch.no_grad()
     def run_chunk(self, n: int):
-        """n rounds of ergm_topp_sample_rows + one step over every slot; one read of the tokens and flags."""
+        """n rounds of ergm_topp_sample_rows (``controls``: ergm_sample_rows) + one step over every slot; one read of
+        the tokens and flags, and of the log-probabilities when a slot keeps them."""
         top_p, eos_id, sp2_id, seed = self._sampling
         B = self.max_batch
         out = torch.empty(n, B, dtype=torch.int64, device=self.dev)
+        lp = None
+        if self.controls and any(a is not None for a in self._lp_acc):
+            lp = torch.zeros(n, B, dtype=torch.float32, device=self.dev)
         if self.engine != "python":
-            L.call("ergm_decode_run_slots", self._plan, n, float(top_p), seed & (2 ** 64 - 1), eos_id, sp2_id,
-                   C.c_void_p(out.data_ptr()), self._stream())
+            if self.controls:
+                L.call("ergm_decode_run_slots_sampled", self._plan, n, float(top_p), C.byref(self._ctl), seed & (2 ** 64 - 1),
+                       eos_id, sp2_id, C.c_void_p(out.data_ptr()), None if lp is None else C.c_void_p(lp.data_ptr()),
+                       self._stream())
+            else:
+                L.call("ergm_decode_run_slots", self._plan, n, float(top_p), seed & (2 ** 64 - 1), eos_id, sp2_id,
+                       C.c_void_p(out.data_ptr()), self._stream())
         else:
             tt = torch.full((B,), sp2_id, dtype=torch.int64, device=self.dev)
+            V = self.m.layout.vocab
             for i in range(n):
-                ops.topp_sample_rows(self._logits, self.m.layout.vocab, top_p, seed, self.row_ids, self.row_steps, eos_id,
-                                     finished=self.finished, tokens=out[i])
+                if self.controls:
+                    ops.sample_rows(self._logits, V, top_p, seed, self.row_ids, self.row_steps, eos_id, ctl=self._ctl,
+                                    finished=self.finished, tokens=out[i], logprob=None if lp is None else lp[i])
+                else:
+                    ops.topp_sample_rows(self._logits, V, top_p, seed, self.row_ids, self.row_steps, eos_id,
+                                         finished=self.finished, tokens=out[i])
                 self.step(out[i], tt)
-        both = torch.cat([out.reshape(-1), self.finished.to(torch.int64)]).cpu()
-        return both[:n * B].view(n, B).tolist(), both[n * B:].tolist()
+        parts = [out.reshape(-1), self.finished.to(torch.int64)]
+        if lp is not None:   # the f32 bits ride along in the one copy
+            parts.append(lp.view(torch.int32).reshape(-1).to(torch.int64))
+        both = torch.cat(parts).cpu()
+        if lp is not None:
+            rows = both[n * B + B:].to(torch.int32).view(torch.float32).view(n, B).tolist()
+            for s, acc in enumerate(self._lp_acc):
+                if acc is not None:
+                    acc.extend(row[s] for row in rows)
+        return both[:n * B].view(n, B).tolist(), both[n * B:n * B + B].tolist()
 
     def admit_requests(self, slots, requests) -> None:
-        self.admit(slots, [r.payload for r in requests], [r.max_new for r in requests], [r.id for r in requests])
+        self.admit(slots, [r.payload for r in requests], [r.max_new for r in requests], [r.id for r in requests],
+                   [r.sampling for r in requests] if self.controls else None)
 
     def extend_requests(self, slots, requests) -> None:
-        self.extend(slots, [r.payload for r in requests], [r.max_new for r in requests], [r.past for r in requests])
+        self.extend(slots, [r.payload for r in requests], [r.max_new for r in requests], [r.past for r in requests],
+                    [r.sampling for r in requests] if self.controls else None)
 
     def retire(self, slot: int, request) -> None:
         if self.keep_logits:
             self.final_logits[request.id] = self.logits[slot].clone()
+        if self.controls and self._lp_acc[slot] is not None:   # the chunk ran on past the request's last token
+            self.token_logprobs[request.id] = self._lp_acc[slot][:len(request.tokens)]
+            self._lp_acc[slot] = None
 
     # ---- requests -----------------------------------------------------------------------------------------
+    def _check_sampling(self, sampling) -> None:
+        if sampling is not None and not self.controls:
+            raise ValueError("sampling parameters need ContinuousGenerator(controls=True)")
+        if sampling is not None and not isinstance(sampling, SamplingParams):
+            raise ValueError("sampling must be a SamplingParams")
+
     def submit(self, prompt, max_new_tokens: Optional[int] = None, request_id: Optional[int] = None,
-               keep: bool = False) -> int:
+               keep: bool = False, sampling: Optional[SamplingParams] = None) -> int:
         """Queue a prompt; returns its id (uint32; arrival order unless given).  ``keep``: the request keeps its slot
         and its cache when it ends (it is parked), so that ``extend_request`` can continue the conversation; a kept
         prompt that carries visual / audio features has at least 2 tokens (the positions the features sit at)."""
         if keep and prompt[3] is not None and int(prompt[0].numel()) < 2:
             raise ValueError("a kept prompt with visual / audio features needs at least 2 tokens")
-        return self.sched.submit(int(prompt[0].numel()), int(prompt[2].numel()), max_new_tokens, request_id, prompt, keep)
+        self._check_sampling(sampling)
+        return self.sched.submit(int(prompt[0].numel()), int(prompt[2].numel()), max_new_tokens, request_id, prompt, keep,
+                                 sampling=sampling)
 
     def extend_request(self, request_id: int, ids, token_types, max_new_tokens: Optional[int] = None,
-                       keep: bool = True) -> int:
+                       keep: bool = True, sampling: Optional[SamplingParams] = None) -> int:
         """Queue the next turn of a parked request: ``ids`` / ``token_types`` are appended behind what its cache holds
         (the tokens of the earlier turns; an eos the model drew is not among them, so a turn that wants it as a
         separator begins with it), and up to max_new_tokens are generated behind them at the next ``run`` / ``drain``,
         returned under the same id.  Raises ValueError when the id is not parked, the turn is empty or longer than
-        max_admit_tokens, or the cache has no room for it and one new token."""
+        max_admit_tokens, or the cache has no room for it and one new token.  ``sampling`` (``controls=True``): None
+        keeps the session's values, except that the new turn has no minimum length."""
         ids, token_types = ids.reshape(-1), token_types.reshape(-1)
         if ids.numel() != token_types.numel():
             raise ValueError("one token type per token")
-        return self.sched.extend(request_id, int(ids.numel()), max_new_tokens, (ids, token_types), keep)
+        self._check_sampling(sampling)
+        return self.sched.extend(request_id, int(ids.numel()), max_new_tokens, (ids, token_types), keep, sampling=sampling)
 
     def release(self, request_id: int) -> None:
         """Free the slot of a parked request."""
@@ -1041,10 +1182,14 @@ class ContinuousGenerator:
         """Serve the queue; returns {id: tokens}, each list ending at its first eos (included) or at its bound."""
         return dict(self.drain(top_p, eos_id, sp2_id, seed))
 
-    def generate(self, prompts, top_p: float, eos_id: int, sp2_id: int, seed: int = 0, max_new_tokens=None) -> List[List[int]]:
-        """One token list per prompt, in submission order.  max_new_tokens: None, one bound for all, or one per prompt."""
+    def generate(self, prompts, top_p: float, eos_id: int, sp2_id: int, seed: int = 0, max_new_tokens=None,
+                 sampling=None) -> List[List[int]]:
+        """One token list per prompt, in submission order.  max_new_tokens: None, one bound for all, or one per prompt;
+        sampling (``controls=True``): None, one ``SamplingParams`` for all, or one per prompt."""
         if max_new_tokens is None or isinstance(max_new_tokens, int):
             max_new_tokens = [max_new_tokens] * len(prompts)
-        ids = [self.submit(p, k) for p, k in zip(prompts, max_new_tokens)]
+        if sampling is None or isinstance(sampling, SamplingParams):
+            sampling = [sampling] * len(prompts)
+        ids = [self.submit(p, k, sampling=sp) for p, k, sp in zip(prompts, max_new_tokens, sampling)]
         out = self.run(top_p, eos_id, sp2_id, seed)
         return [out[i] for i in ids]

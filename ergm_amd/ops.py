@@ -505,6 +505,58 @@ def topp_sample_rows(logits, V: int, top_p: float, seed: int, row_ids, row_steps
     return tokens
 
 
+def sample_ctl(top_p=None, temperature=None, rep_penalty=None, top_k=None, min_step=None, seen=None) -> L.SampleCtl:
+    """ergm_sample_ctl over per-row device tensors: top_p / temperature / rep_penalty f32 [B], top_k int32 [B],
+    min_step int32 [B] (uint32 bits), seen int32 [B, >= ceil(V / 32)] (uint32 bits); None is the default of every
+    row.  The struct holds addresses only: the caller keeps the tensors alive."""
+    for t, dt in ((top_p, torch.float32), (temperature, torch.float32), (rep_penalty, torch.float32), (top_k, torch.int32),
+                  (min_step, torch.int32), (seen, torch.int32)):
+        if t is not None:
+            _need_gpu(t)
+            assert t.dtype == dt and t.is_contiguous()
+    assert seen is None or seen.dim() == 2
+    p = lambda t: None if t is None else t.data_ptr()
+    return L.SampleCtl(p(top_p), p(temperature), p(rep_penalty), p(top_k), p(min_step), p(seen),
+                       0 if seen is None else seen.stride(0))
+
+
+def sample_rows(logits, V: int, top_p: float, seed: int, row_ids, row_steps, eos_id: int, ctl: Optional[L.SampleCtl] = None,
+                finished=None, tokens=None, kept=None, kept_mass=None, logprob=None):
+    """``topp_sample_rows`` with per-row sampling controls (ergm_sample_rows): ``ctl`` from ``sample_ctl`` (None: every
+    default, the old sampler's outputs); ``logprob`` (f32 [B], optional) receives the drawn tokens' log-probabilities."""
+    _need_gpu(logits, row_ids, row_steps)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    assert finished is None or finished.dtype == torch.uint8
+    assert logprob is None or (logprob.dtype == torch.float32 and logprob.is_contiguous())
+    B = logits.shape[0]
+    for t in (row_ids, row_steps):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
+    if tokens is None:
+        tokens = torch.empty(B, dtype=torch.int64, device=logits.device)
+    L.call("ergm_sample_rows", _ptr(logits), logits.stride(0), B, V, float(top_p), None if ctl is None else C.byref(ctl),
+           seed & (2 ** 64 - 1), _ptr(row_ids), _ptr(row_steps), _ptr(finished), eos_id, _ptr(tokens), _ptr(kept),
+           _ptr(kept_mass), _ptr(logprob), _stream(logits.device))
+    return tokens
+
+
+def sample_mark(ids, slot, start, length, V: int, seen=None, reset=None, min_new=None, row_steps=None, min_step=None,
+                n_slots: Optional[int] = None):
+    """Record the packed ``ids`` (int64 [total]) of n_seq sequences in the bitmap rows of their slots and set the slots'
+    minimum length (ergm_sample_mark): slot / start / length (and reset / min_new, optional) int32 [n_seq] on the device;
+    seen int32 [n_slots, >= ceil(V / 32)]; min_step[slot] = row_steps[slot] + min_new (int32 [n_slots], uint32 bits)."""
+    _need_gpu(ids, slot, start, length)
+    assert ids.dtype == torch.int64 and ids.is_contiguous()
+    for t in (slot, start, length, reset, min_new):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() == slot.numel())
+    for t in (seen, row_steps, min_step):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous())
+    if n_slots is None:
+        n_slots = seen.shape[0] if seen is not None else min_step.numel()
+    L.call("ergm_sample_mark", _ptr(ids), ids.numel(), _ptr(slot), _ptr(start), _ptr(length), _ptr(reset), _ptr(min_new),
+           slot.numel(), V, n_slots, _ptr(seen), 0 if seen is None else seen.stride(0), _ptr(row_steps), _ptr(min_step),
+           _stream(ids.device))
+
+
 def feat_pool(x: torch.Tensor, lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """Mean over frames of encoder outputs x [B, T, D] (f32 / bf16, any row strides with unit
     last-dim stride) -> [B, D] f32; ``lengths`` [B] int32 limits each sample to its valid frames.

@@ -107,14 +107,15 @@ class Trainer:
 
     @torch.no_grad()
     def test(self, loader, top_p: float, eos_id: int, sp2_id: int, seed: int = 0, max_batch: int = 8,
-             max_len: Optional[int] = None, engine: str = "python"):
+             max_len: Optional[int] = None, engine: str = "python", sampling=None):
         """The reference's ``test()`` (src/main.py:291-335) without the tokenizer: one sampled response for every
         sample of ``loader``, all of them served by one ``ContinuousGenerator`` of ``max_batch`` slots.  A sample's
         prompt is its first n tokens, n = the count of tokens that are not ``eos_id`` (the collate pads with eos), with
         its token types, its caption row and its visual / audio features; its draws are keyed by its index in the
         loader, so seeded runs repeat.  Returns (hypothesis ids, reference ids = ``labels != -100``, emotion labels, the
         per-batch LM losses of the inference forward ``validation`` runs), lists in loader order.  Decoding the ids
-        to text is the caller's."""
+        to text is the caller's.  ``sampling``: one ``SamplingParams`` for every sample (None: plain
+        top-p, the sampler and the launches of before)."""
         from .generate import ContinuousGenerator
         self.model.eval()
         dev = self.device
@@ -136,8 +137,9 @@ class Trainer:
         if max_len is None:
             max_len = self.model.config.n_positions
         gen = ContinuousGenerator(self.model, max_batch=max_batch, max_len=max_len,
-                                  cap_max=max(int(p[2].numel()) for p in prompts), engine=engine)
-        hyps = gen.generate(prompts, top_p, eos_id, sp2_id, seed)
+                                  cap_max=max(int(p[2].numel()) for p in prompts), engine=engine,
+                                  controls=sampling is not None)
+        hyps = gen.generate(prompts, top_p, eos_id, sp2_id, seed, sampling=sampling)
         return hyps, refs, emos, [float(x) for x in torch.stack(losses).tolist()]
 
     def train(self, train_loader, valid_loader, num_epochs: int, log=print,

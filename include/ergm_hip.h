@@ -26,6 +26,7 @@
  *   ergm_attn_decode, ergm_embed_rows, ergm_topp_sample,
  *   ergm_attn_fwd_ragged, ergm_embed_packed, ergm_rows_to_slots, ergm_topp_sample_rows
  *   ergm_attn_fwd_extend, ergm_rows_to_slots_at, ergm_decode_extend (later additions, same version)
+ *   ergm_sample_rows, ergm_sample_mark, ergm_decode_run_slots_sampled (per-request sampling controls, same version)
  *                         the per-token work of nucleus_sampling (src/main.py:253-282), for a batch
  *   ergm_linear_rows      Conv1D / lm_head for the few rows of a decode step, with the nn.LayerNorm in front
  *                         of it (src/model.py:298,318,332) computed in the same launch
@@ -373,6 +374,52 @@ int ergm_topp_sample(const float* logits, int ldl, int B, int V, float top_p, ui
 int ergm_topp_sample_rows(const float* logits, int ldl, int B, int V, float top_p, uint64_t seed,
                           const uint32_t* row_ids, const uint32_t* row_steps, void* finished, int64_t eos_id,
                           int64_t* tokens, int* kept, float* kept_mass, void* stream);
+/* The per-row sampling controls of ergm_sample_rows: device arrays of one value per row [B], any of them NULL for the
+ * default of every row, and the bitmap of the tokens each row has seen (uint32 [B][ld_seen], token j = bit j & 31 of
+ * word j >> 5, ld_seen >= (V + 31) / 32 words; NULL: no token is penalised and none is recorded).                */
+typedef struct {
+    const float* top_p;        /* default: the scalar argument */
+    const float* temperature;  /* default 1 */
+    const float* rep_penalty;  /* default 1 */
+    const int* top_k;          /* default 0: off */
+    const uint32_t* min_step;  /* default 0: eos may be drawn at once */
+    uint32_t* seen;
+    int ld_seen;
+} ergm_sample_ctl;
+/* ergm_topp_sample_rows with sampling controls per row (found by symbol, ABI unchanged).  For row b, x_j =
+ * logits[b][j], j < V, in this order (the usual order of logits processors):
+ *   1. repetition penalty r = rep_penalty[b]: for every j whose bit is set in seen[b], x_j <- x_j · r if x_j < 0,
+ *      else x_j / r;
+ *   2. minimum length: while row_steps[b] < min_step[b] the token eos_id holds no mass, is not counted in `kept` and
+ *      cannot be drawn;
+ *   3. temperature: x_j <- x_j / temperature[b], an f32 IEEE division (temperature = 1 and r = 1 change no bit);
+ *   4. masses: e_j = expf(x_j - max_j x_j), q_j = floor(e_j · 2^30), S = sum q_j: ergm_topp_sample's integers;
+ *   5. rank: descending value, ties by ascending token id;
+ *   6. top-k, k = top_k[b]: with k >= 1 only the ranks < k remain and S_k is their mass; otherwise S_k = S;
+ *   7. top-p: rank r is kept iff it remains under top-k and (r == 0 or the mass of the ranks < r is <= T), T from
+ *      top_p[b] by ergm_topp_sample's expression with S_k in the place of S: top-p over the renormalised top-k set;
+ *   8. the draw: ergm_topp_sample_rows', counter {row_ids[b], 0, 0xE5A3, row_steps[b]}: the first kept token in
+ *      ascending id whose running kept mass reaches ceil(u · K), K the kept mass.
+ * top_k = 1 is greedy decoding: the arg-max, the lowest id on ties, whatever the seed.  A temperature or penalty that
+ * is NaN, infinite or <= 0 acts as 1; top_k <= 0 or >= the number of tokens with mass (q_j > 0) is off; no value
+ * makes the kernel follow an index out of a table.  ctl may be NULL: every output is then ergm_topp_sample_rows'.
+ * logprob (f32 [B], optional): (x_tok - max) - ln(S · 2^-30), the log-probability of the drawn token under the
+ * processed distribution before truncation, 0 for a finished row.  kept and kept_mass (K / S) keep their meaning.
+ * With ctl->seen a live row sets the bit of the token it drew (eos included) in the same launch; a finished row sets
+ * nothing.                                                                                                        */
+int ergm_sample_rows(const float* logits, int ldl, int B, int V, float top_p, const ergm_sample_ctl* ctl, uint64_t seed,
+                     const uint32_t* row_ids, const uint32_t* row_steps, void* finished, int64_t eos_id,
+                     int64_t* tokens, int* kept, float* kept_mass, float* logprob, void* stream);
+/* The bitmap and the minimum length of the slots an admission or an extension filled, one launch: sequence b < n_seq
+ * (device int [n_seq] each: slot, start, len over the packed device int64 ids [total]; reset and min_new may be NULL)
+ * clears row slot[b] of seen when reset[b] != 0, then sets the bit of each of its ids, and writes min_step[slot[b]] =
+ * row_steps[slot[b]] + max(min_new[b], 0), so that a minimum length counts from the start of the turn (min_step and
+ * row_steps uint32 [n_slots], both NULL to leave the minimum alone).  Clamped like ergm_rows_to_slots: len to [0,
+ * total], start to the packed extent, an id outside [0, V) sets nothing, a slot outside [0, n_slots) writes nothing.
+ * Found by symbol (ABI unchanged).                                                                                 */
+int ergm_sample_mark(const int64_t* ids, int total, const int* slot, const int* start, const int* len, const int* reset,
+                     const int* min_new, int n_seq, int V, int n_slots, uint32_t* seen, int ld_seen,
+                     const uint32_t* row_steps, uint32_t* min_step, void* stream);
 /* Packed rows into per-slot buffers: row t < len[b] of sequence b (row start[b] + t of src, ld_src bytes apart) is
  * copied to dst + slot[b]·ld_slot + t·ld_row (bytes), row_bytes bytes in 16-byte pieces.  start / len / slot: device
  * int [n_seq]; total_rows = the rows of src, max_rows = the host's bound on len (it sizes the grid).  len is clamped
@@ -800,6 +847,11 @@ int ergm_decode_step_slots(ergm_decode_plan* plan, const int64_t* tokens, const 
  * back: the host looks at tokens_out and finished when it chooses.                                                */
 int ergm_decode_run_slots(ergm_decode_plan* plan, int n, float top_p, uint64_t seed, int64_t eos_id, int64_t sp2_id,
                           int64_t* tokens_out, void* stream);
+/* ergm_decode_run_slots with ergm_sample_rows(ctl, may be NULL) in the place of ergm_topp_sample_rows: the same loop,
+ * the same stream discipline and the same launch counts.  logprobs_out: device f32 [n][max_batch] or NULL.  Found by
+ * symbol (ABI unchanged).                                                                                          */
+int ergm_decode_run_slots_sampled(ergm_decode_plan* plan, int n, float top_p, const ergm_sample_ctl* ctl, uint64_t seed,
+                                  int64_t eos_id, int64_t sp2_id, int64_t* tokens_out, float* logprobs_out, void* stream);
 
 /* Library information and errors. */
 int ergm_version(void);

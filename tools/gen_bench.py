@@ -32,11 +32,19 @@ new tokens per turn, on ContinuousGenerator(max_batch=32, max_len=192), engines 
   resubmit   what a user does without it: every turn is a new request carrying the whole history (the baseline)
 tokens/s = the 2,048 requested tokens over the four turns of all sessions, the two ways alternating in one process,
 median of 5 after a warm-up each; ``prefill_rows`` = the packed rows each turn's prefill ran over.
+Sampling controls: the same 256 requests on ContinuousGenerator(controls=True),
+  bd32/nd32/fd32  every request with the default SamplingParams (the new sampler, nothing asked of it)
+  bx32/nx32/fx32  every request with top_k=50, temperature=0.8, repetition_penalty=1.2
+and ``sample``: the sampler launch alone at B = 32, V = 50,257 on the logits an admission of 32 such prompts leaves,
+microseconds per launch in back-to-back windows of 200, the variants alternating inside every repeat: ergm_topp_sample_rows
+(old), ergm_sample_rows with no controls (defaults), top_k=50 only, repetition_penalty=1.2 only (the prompt's ids seen),
+and everything (top_k=50, temperature=0.8, repetition_penalty=1.2).
 Without --case the tool runs every case in turn, each in a fresh child process under its own timeout, one at a
 time, and stops at the first that fails.  --cases a,b,c runs those cases in that
 order (e.g. b32,n32,f32,b32,n32,f32 to alternate engines on one box).  For the kernel-time split of one engine:
   rocprofv3 --kernel-trace --stats -d OUT -- python tools/gen_bench.py --case f32
-Usage (GPU box): python tools/gen_bench.py [--case kv|b1|b8|b32|n*|f*|attn|bs32|bc32|n?32|f?32|admit|turns] [--cases LIST]"""
+Usage (GPU box): python tools/gen_bench.py [--case kv|b1|b8|b32|n*|f*|attn|bs32|bc32|bd32|bx32|n?32|f?32|admit|turns|sample]
+                 [--cases LIST]"""
 import json
 import os
 import statistics
@@ -47,11 +55,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 ENGINES = {"b": "python", "n": "native", "f": "fused"}
 CASES = {"kv": 240, **{e + b: 240 for e in ENGINES for b in ("1", "8", "32")}, "attn": 240,   # seconds a child may take
-         **{e + m + "32": 300 for e in ENGINES for m in "sc"}, "admit": 240, "turns": 420}
+         **{e + m + "32": 300 for e in ENGINES for m in "scdx"}, "admit": 240, "turns": 420, "sample": 240}
 N_REQ, REQ_MEAN = 256, 16
 PROMPT = CAPS = NEW = 64
 TOP_P, NO_EOS, SP2 = 0.95, -1, 50259
 REPEATS = 5
+EVERYTHING = dict(top_k=50, temperature=0.8, repetition_penalty=1.2)   # the controls of the x cases
 
 
 def _event_ms(fn):
@@ -112,7 +121,7 @@ def _setup_requests(n):
 
 
 def _requests(case):
-    from ergm_amd.generate import BatchedGenerator, ContinuousGenerator
+    from ergm_amd.generate import BatchedGenerator, ContinuousGenerator, SamplingParams
     dev, model, prompts, new = _setup_requests(N_REQ)
     engine, B = ENGINES[case[0]], int(case[2:])
     steps, admits = [0], [N_REQ // B]
@@ -128,11 +137,14 @@ def _requests(case):
                 assert [len(r) for r in out] == new[i:i + B]
                 steps[0] += k - 1
     else:
-        gen = ContinuousGenerator(model, max_batch=B, max_len=PROMPT + NEW, cap_max=CAPS, engine=engine)
+        gen = ContinuousGenerator(model, max_batch=B, max_len=PROMPT + NEW, cap_max=CAPS, engine=engine,
+                                  controls=case[1] in "dx")
+        sampling = {"c": None, "d": SamplingParams(), "x": SamplingParams(**EVERYTHING)}[case[1]]
 
         def run():
             s0, a0 = gen.sched.steps, gen.admit_calls
-            out = gen.generate(prompts, top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2, seed=7, max_new_tokens=new)
+            out = gen.generate(prompts, top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2, seed=7, max_new_tokens=new,
+                               sampling=sampling)
             assert [len(r) for r in out] == new
             steps[0], admits[0] = gen.sched.steps - s0, gen.admit_calls - a0
     run()
@@ -181,6 +193,51 @@ def _admission():
             fn()
             row[name] = round(statistics.median(_event_ms(fn) for _ in range(REPEATS)) / N * 1e3, 2)
         print(json.dumps(row), flush=True)
+
+
+def _sampler():
+    import torch
+    from ergm_amd import ops
+    from ergm_amd.generate import ContinuousGenerator
+    dev, model, prompts, _ = _setup_requests(32)
+    B, N = 32, 200
+    gen = ContinuousGenerator(model, max_batch=B, max_len=PROMPT + NEW, cap_max=CAPS, engine="native")
+    gen.admit(list(range(B)), prompts)
+    logits, V = gen._logits, 50257   # GPT-2's own vocabulary: the model's added special tokens stay out of the draw
+    rid = torch.arange(B, dtype=torch.int32, device=dev)
+    steps = torch.zeros(B, dtype=torch.int32, device=dev)
+    tokens = torch.empty(B, dtype=torch.int64, device=dev)
+    f = lambda v: torch.full((B,), v, dtype=torch.float32, device=dev)
+    top_k, temp, pen = torch.full((B,), EVERYTHING["top_k"], dtype=torch.int32, device=dev), f(EVERYTHING["temperature"]), \
+        f(EVERYTHING["repetition_penalty"])
+
+    def bitmap():   # the prompts' ids, as an admission marks them
+        seen = torch.zeros(B, (V + 31) // 32, dtype=torch.int32, device=dev)
+        ids = torch.cat([p[0].reshape(-1) for p in prompts])
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+        ops.sample_mark(ids, i32(list(range(B))), i32([b * PROMPT for b in range(B)]), i32([PROMPT] * B), V, seen=seen)
+        return seen
+    ctls = {"defaults": None, "top_k": ops.sample_ctl(top_k=top_k), "penalty": ops.sample_ctl(rep_penalty=pen, seen=bitmap()),
+            "everything": ops.sample_ctl(top_k=top_k, temperature=temp, rep_penalty=pen, seen=bitmap())}
+
+    def window(name):
+        def run():
+            for _ in range(N):
+                if name == "old":
+                    ops.topp_sample_rows(logits, V, TOP_P, 7, rid, steps, NO_EOS, tokens=tokens)
+                else:
+                    ops.sample_rows(logits, V, TOP_P, 7, rid, steps, NO_EOS, ctl=ctls[name], tokens=tokens)
+        return run
+    names = ["old", *ctls]
+    us = {n: [] for n in names}
+    for rep in range(REPEATS + 1):   # alternating; the first of each is the warm-up
+        for n in names:
+            t = _event_ms(window(n)) / N * 1e3
+            if rep:
+                us[n].append(t)
+    for n in names:
+        print(json.dumps({"case": "sample", "variant": n, "B": B, "V": V, "us_per_launch": round(statistics.median(us[n]), 2),
+                          "us_all": [round(x, 2) for x in us[n]]}), flush=True)
 
 
 SESSIONS, TURNS, TURN_ROWS, TURN_NEW = 32, 4, 16, 16
@@ -282,7 +339,9 @@ def main():
             _admission()
         elif case == "turns":
             _turns()
-        elif len(case) == 4 and case[1] in "sc":
+        elif case == "sample":
+            _sampler()
+        elif len(case) == 4 and case[1] in "scdx":
             _requests(case)
         else:
             _generation(case)
