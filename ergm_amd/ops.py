@@ -261,13 +261,19 @@ def attn_fwd(q, k, v, B, H, Sq, Sk, causal, o=None, lse=None, dropout: Optional[
 
 
 def attn_bwd(q, k, v, o, dout, lse, B, H, Sq, Sk, causal, dq=None, dk=None, dv=None,
-             dropout: Optional[L.Dropout] = None, keep_bits: Optional[torch.Tensor] = None):
+             dropout: Optional[L.Dropout] = None, keep_bits: Optional[torch.Tensor] = None,
+             delta: Optional[torch.Tensor] = None):
+    """``delta`` (f32, B*H*Sq elements): where the tiled kernels leave rowsum(dO∘O) (the short kernel keeps it in LDS);
+    a scratch buffer by default."""
     _need_gpu(q, k, v, o, dout, lse)
     dev = q.device
     dq = torch.empty(B * Sq, H * 64, dtype=torch.bfloat16, device=dev) if dq is None else dq
     dk = torch.empty(B * Sk, H * 64, dtype=torch.bfloat16, device=dev) if dk is None else dk
     dv = torch.empty(B * Sk, H * 64, dtype=torch.bfloat16, device=dev) if dv is None else dv
-    delta = torch.empty(B, H, Sq, dtype=torch.float32, device=dev)
+    if delta is None:
+        delta = torch.empty(B, H, Sq, dtype=torch.float32, device=dev)
+    elif not delta.is_cuda or delta.dtype != torch.float32 or delta.numel() < B * H * Sq or not delta.is_contiguous():
+        raise ValueError("attn_bwd: delta is a contiguous f32 GPU tensor of at least B*H*Sq elements")
     L.call("ergm_attn_bwd", _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(dout), _ptr(lse), _ptr(delta), _ptr(dq), _ptr(dk),
            _ptr(dv), B, H, Sq, Sk, q.stride(0), k.stride(0), v.stride(0), o.stride(0), dout.stride(0), dq.stride(0),
            dk.stride(0), dv.stride(0), int(bool(causal)), _dp(dropout), _ptr(keep_bits), _stream(dev))
