@@ -246,6 +246,19 @@ __device__ __forceinline__ float stored_keep(const uint64_t* mrow, int key, floa
     return ((mrow[key >> 6] >> (key & 63)) & 1ull) ? scale : 0.f;
 }
 
+// This lane's 16 of the 64 elements of its query's normalised output row (bf16); Ob = the row's first element of the
+// head, formed by the caller for a live query only.  inv = 1 / l, or 0 for a row without keys.
+__device__ __forceinline__ void fwd_store_row(__bf16* Ob, const f32x4 (&o)[4], float inv) {
+    const int g = (threadIdx.x & 63) >> 4;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        bf16x4 w;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w[r] = f2bf(o[d][r] * inv);
+        *reinterpret_cast<bf16x4*>(Ob + d * 16 + 4 * g) = w;
+    }
+}
+
 // Normalised output row (bf16) and the log-sum-exp (natural log, scaled scores) of this lane's query.
 // LSE = false (the ragged inference forward without an LSE buffer): the row only.
 template <bool LSE = true>
@@ -281,14 +294,7 @@ __device__ __forceinline__ void fwd_store(const AttnArgs& a, int b, int h, int q
         }
     }
     if (q >= a.Sq) return;
-    __bf16* Ob = a.out + ((size_t)b * a.Sq + q) * a.ldo + h * AT_D;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        bf16x4 w;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) w[r] = f2bf(o[d][r] * inv);
-        *reinterpret_cast<bf16x4*>(Ob + d * 16 + 4 * g) = w;
-    }
+    fwd_store_row(a.out + ((size_t)b * a.Sq + q) * a.ldo + h * AT_D, o, inv);
     if constexpr (LSE)
         if (g == 0) a.lse[((size_t)b * a.H + h) * a.Sq + q] = m * a.scale + logf(l);
 }
@@ -463,6 +469,32 @@ __device__ __forceinline__ void ring_sync(int after) {
     __builtin_amdgcn_s_barrier();
 }
 
+// The forward's key loop, the one copy every forward kernel runs: zero the lane's Oᵀ column and softmax state, then
+// walk key tiles 0 .. nkt - 1 of K | V (rows < Sk of Kb / Vb) through the NS-stage LDS-DMA ring, fwd_tile on each.
+// q = this lane's query, qw0 = the first query of its wave; mrow = the lane's dropout mask row or null.  What a lane
+// ends with depends on its own arguments alone, so two kernels that call this with the same ones give the same bits.
+template <bool CAUSAL, int NS, bool DROP>
+__device__ __forceinline__ void fwd_keys(char* ring, const __bf16* Kb, int ldk, const __bf16* Vb, int ldv, int Sk, int nkt,
+                                         int wave, int q, int qw0, float c, const bf16x8 (&qf)[2], f32x4 (&o)[4], float& m,
+                                         float& l, const DropSite& drop, int64_t arow, uint64_t* mrow) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    m = -INFINITY, l = 0.f;
+    auto issue = [&](int kt) {
+        char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
+        AttnTile::issue(st, Kb, ldk, kt * AT_T, Sk, 0, wave);
+        AttnTile::issue(st + AT_TILE_BYTES, Vb, ldv, kt * AT_T, Sk, 0, wave);
+    };
+    for (int s = 0; s < NS - 1 && s < nkt; ++s) issue(s);
+    for (int kt = 0; kt < nkt; ++kt) {
+        ring_sync<4, NS>(min(NS - 2, nkt - 1 - kt));
+        if (kt + NS - 1 < nkt) issue(kt + NS - 1);
+        const char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
+        fwd_tile<CAUSAL, DROP>(st, st + AT_TILE_BYTES, kt * AT_T, q, qw0, Sk, c, qf, o, m, l, drop, arow,
+                               mrow ? mrow + kt : nullptr);
+    }
+}
+
 template <bool CAUSAL, int NS, bool DROP>
 __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_fwd_kernel(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) char ring[NS * 2 * AT_TILE_BYTES];  // [stage][K|V]
@@ -484,31 +516,17 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_fwd_kernel(AttnArgs a)
     vm_ready(qf[0]);
     vm_ready(qf[1]);
 
-    f32x4 o[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = -INFINITY, l = 0.f;
-
     int nkt = (a.Sk + AT_T - 1) / AT_T;
     if (CAUSAL) {
         int qlast = min(a.Sq, qblk + AT_T) - 1;
         nkt = min(nkt, qlast / AT_T + 1);
     }
-    auto issue = [&](int kt) {
-        char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
-        AttnTile::issue(st, Kb, a.ldk, kt * AT_T, a.Sk, 0, wave);
-        AttnTile::issue(st + AT_TILE_BYTES, Vb, a.ldv, kt * AT_T, a.Sk, 0, wave);
-    };
     const int64_t arow = ((int64_t)b * a.H + h) * a.Sq + q;  // dropout row of this lane's query
     uint64_t* mrow = DROP && q < a.Sq ? a.mbits + arow * a.mwords : nullptr;
-    for (int s = 0; s < NS - 1 && s < nkt; ++s) issue(s);
-    for (int kt = 0; kt < nkt; ++kt) {
-        ring_sync<4, NS>(min(NS - 2, nkt - 1 - kt));
-        if (kt + NS - 1 < nkt) issue(kt + NS - 1);
-        const char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
-        fwd_tile<CAUSAL, DROP>(st, st + AT_TILE_BYTES, kt * AT_T, q, qblk + wave * 16, a.Sk, c, qf, o, m, l, a.drop,
-                               arow, mrow ? mrow + kt : nullptr);
-    }
+    f32x4 o[4];
+    float m, l;
+    fwd_keys<CAUSAL, NS, DROP>(ring, Kb, a.ldk, Vb, a.ldv, a.Sk, nkt, wave, q, qblk + wave * 16, c, qf, o, m, l, a.drop, arow,
+                               mrow);
     fwd_store(a, b, h, q, o, m, l);
 }
 
@@ -517,8 +535,8 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_fwd_kernel(AttnArgs a)
 // k_start[b] + k_len[b] - 1 of the packed K / V buffers.  The grid is rectangular, (query tiles of the longest
 // sequence, H, sequences); a workgroup whose tile lies past its sequence's last row exits before it touches memory
 // or a barrier.  Query tiles are counted from the sequence's own first row (causal: the last tile, the longest key
-// loop, first), so the workgroup of (sequence, tile, head) runs attn_fwd_kernel's loop on the tiles attn_fwd_kernel
-// sees for that sequence alone (B = 1, Sq = q_len[b], Sk = k_len[b]): the output rows are bitwise the same.
+// loop, first), so the workgroup of (sequence, tile, head) calls fwd_keys with the arguments attn_fwd_kernel gives it
+// for that sequence alone (B = 1, Sq = q_len[b], Sk = k_len[b]): one loop, the output rows are bitwise the same.
 // Everything read from the metadata arrays is clamped to the packed extents before an address is formed.
 struct RaggedMeta {
     const int *q_start, *q_len, *k_start, *k_len;
@@ -555,29 +573,15 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_ragged_kernel(AttnArgs a, Rag
     vm_ready(qf[0]);
     vm_ready(qf[1]);
 
-    f32x4 o[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = -INFINITY, l = 0.f;
-
     int nkt = (a.Sk + AT_T - 1) / AT_T;
     if (CAUSAL) {
         int qlast = min(a.Sq, qblk + AT_T) - 1;
         nkt = min(nkt, qlast / AT_T + 1);
     }
-    auto issue = [&](int kt) {
-        char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
-        AttnTile::issue(st, Kb, a.ldk, kt * AT_T, a.Sk, 0, wave);
-        AttnTile::issue(st + AT_TILE_BYTES, Vb, a.ldv, kt * AT_T, a.Sk, 0, wave);
-    };
-    for (int s = 0; s < NS - 1 && s < nkt; ++s) issue(s);
-    for (int kt = 0; kt < nkt; ++kt) {
-        ring_sync<4, NS>(min(NS - 2, nkt - 1 - kt));
-        if (kt + NS - 1 < nkt) issue(kt + NS - 1);
-        const char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
-        fwd_tile<CAUSAL, false>(st, st + AT_TILE_BYTES, kt * AT_T, q, qblk + wave * 16, a.Sk, c, qf, o, m, l, a.drop, 0,
+    f32x4 o[4];
+    float m, l;
+    fwd_keys<CAUSAL, NS, false>(ring, Kb, a.ldk, Vb, a.ldv, a.Sk, nkt, wave, q, qblk + wave * 16, c, qf, o, m, l, a.drop, 0,
                                 nullptr);
-    }
     fwd_store<LSE>(a, 0, h, q, o, m, l);
 }
 
@@ -587,8 +591,8 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_ragged_kernel(AttnArgs a, Rag
 // ABSOLUTE positions, tile t = positions 64t .. 64t + 63, and a sequence runs tiles past / 64 .. ceil(Sk / 64) - 1 (at
 // most ceil(n / 64) + 1 of them, the grid's x extent; the last tile, the longest key loop, first).  The workgroup of
 // (sequence, tile, head) then holds the queries, per wave and lane, that attn_fwd_kernel<causal>(B = 1, Sq = Sk) holds
-// for that tile and walks the same key tiles with the same mask decisions, so output row s is bitwise that call's row
-// past + s.  A lane's column of Sᵀ and Oᵀ depends on its own query alone (the row reductions run over the 4 lanes of
+// for that tile and hands fwd_keys the same q, qw0, Sk and nkt (the same key tiles, the same mask decisions), so output
+// row s is bitwise that call's row past + s.  A lane's column of Sᵀ and Oᵀ depends on its own query alone (the row reductions run over the 4 lanes of
 // one query), so the lanes below `past`, which load zeros and store nothing, do not touch the others.  Tiles counted
 // from the chunk's first row would make the early queries of a tile walk one more, fully masked, key tile, whose
 // rescale exp2(fma(m, c, -m·c)) is not exactly 1.
@@ -624,43 +628,19 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_extend_kernel(AttnArgs a, Rag
     vm_ready(qf[0]);
     vm_ready(qf[1]);
 
-    f32x4 o[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = -INFINITY, l = 0.f;
-
     const int qlast = min(Sk, qblk + AT_T) - 1;
     const int nkt = min((Sk + AT_T - 1) / AT_T, qlast / AT_T + 1);
-    auto issue = [&](int kt) {
-        char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
-        AttnTile::issue(st, Kb, a.ldk, kt * AT_T, Sk, 0, wave);
-        AttnTile::issue(st + AT_TILE_BYTES, Vb, a.ldv, kt * AT_T, Sk, 0, wave);
-    };
-    for (int s = 0; s < NS - 1 && s < nkt; ++s) issue(s);
-    for (int kt = 0; kt < nkt; ++kt) {
-        ring_sync<4, NS>(min(NS - 2, nkt - 1 - kt));
-        if (kt + NS - 1 < nkt) issue(kt + NS - 1);
-        const char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
-        fwd_tile<true, false>(st, st + AT_TILE_BYTES, kt * AT_T, q, qblk + wave * 16, Sk, c, qf, o, m, l, a.drop, 0, nullptr);
-    }
-    if (!mine) return;
-    // fwd_store's row, at the packed row
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
-    __bf16* Ob = a.out + qrow * a.ldo + h * AT_D;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        bf16x4 w;
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) w[rr] = f2bf(o[d][rr] * inv);
-        *reinterpret_cast<bf16x4*>(Ob + d * 16 + 4 * g) = w;
-    }
+    f32x4 o[4];
+    float m, l;
+    fwd_keys<true, NS, false>(ring, Kb, a.ldk, Vb, a.ldv, Sk, nkt, wave, q, qblk + wave * 16, c, qf, o, m, l, a.drop, 0, nullptr);
+    if (mine) fwd_store_row(a.out + qrow * a.ldo + h * AT_D, o, l > 0.f ? 1.0f / l : 0.f);  // fwd_store's row, at the packed row
 }
 
 // Cross-attention forward with the query projection inside (non-causal): the workgroup of (query block, h, b)
 // first forms its 64 x 64 Q tile = bf16(LN_x rows · Wq[:, h·64 ..] + bias) on its 4 waves (2 x 2 grid of 32 x 32,
 // 64-deep K steps through a 3-stage LDS-DMA ring: the product order of the GEMM's 64x64 configuration, so Q is
 // bitwise the q GEMM's output), stores it (the backward's operand) and stages it in LDS for the Q fragments, then
-// runs attn_fwd_kernel's key loop over the same ring.  One launch and one Q round trip fewer per block and chain on
+// runs the forward's key loop (fwd_keys, as attn_fwd_kernel does) over the same ring.  One launch and one Q round trip fewer per block and chain on
 // the forward, which is latency-bound (profiles/r04_experiments.txt #10).
 constexpr int QG_STAGES = 3;
 constexpr int QG_STAGE = 2 * AT_TILE_BYTES;  // A 64 x 64 + W 64 x 64 (bf16)
@@ -742,26 +722,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_qgemm_kernel(AttnArgs a) {
 
     const __bf16* Kb = a.k + (size_t)b * a.Sk * a.ldk + h * AT_D;
     const __bf16* Vb = a.v + (size_t)b * a.Sk * a.ldv + h * AT_D;
-    f32x4 o[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = -INFINITY, l = 0.f;
-    const int nkt = (a.Sk + AT_T - 1) / AT_T;
-    auto issue = [&](int kt) {
-        char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
-        AttnTile::issue(st, Kb, a.ldk, kt * AT_T, a.Sk, 0, wave);
-        AttnTile::issue(st + AT_TILE_BYTES, Vb, a.ldv, kt * AT_T, a.Sk, 0, wave);
-    };
     const int64_t arow = ((int64_t)b * a.H + h) * a.Sq + q;  // dropout row of this lane's query
     uint64_t* mrow = DROP && q < a.Sq ? a.mbits + arow * a.mwords : nullptr;
-    for (int s = 0; s < NS - 1 && s < nkt; ++s) issue(s);
-    for (int kt = 0; kt < nkt; ++kt) {
-        ring_sync<4, NS>(min(NS - 2, nkt - 1 - kt));
-        if (kt + NS - 1 < nkt) issue(kt + NS - 1);
-        const char* st = ring + (kt % NS) * 2 * AT_TILE_BYTES;
-        fwd_tile<false, DROP>(st, st + AT_TILE_BYTES, kt * AT_T, q, qblk + wave * 16, a.Sk, c, qf, o, m, l, a.drop, arow,
-                              mrow ? mrow + kt : nullptr);
-    }
+    f32x4 o[4];
+    float m, l;
+    fwd_keys<false, NS, DROP>(ring, Kb, a.ldk, Vb, a.ldv, a.Sk, (a.Sk + AT_T - 1) / AT_T, wave, q, qblk + wave * 16, c, qf, o, m,
+                              l, a.drop, arow, mrow);
     fwd_store(a, b, h, q, o, m, l);
 }
 

@@ -203,6 +203,7 @@ struct TpShared {
     unsigned long long pick[2];
     float red[TP_THREADS / 64];
     int sel;
+    float mx;  // the row maximum, kept for the log-probability (in the struct's tail padding: the size stays 24,664 B)
 };
 
 // Exclusive prefix sum over the 1,024 threads in thread order (Hillis-Steele in LDS); `total` = the sum.
@@ -232,152 +233,7 @@ __device__ __forceinline__ float tp_use(float e) {
     return e;
 }
 
-// One workgroup per row; thread t holds the `per` consecutive tokens from t·per in registers.
-template <int NPT>
-__global__ __launch_bounds__(TP_THREADS) void topp_sample_kernel(const float* __restrict__ logits, int ldl, int V,
-                                                                 float top_p, uint32_t seed_lo, uint32_t seed_hi,
-                                                                 uint32_t step, const uint32_t* __restrict__ row_ids,
-                                                                 const uint32_t* __restrict__ row_steps, uint8_t* finished,
-                                                                 int64_t eos_id, int64_t* __restrict__ tokens,
-                                                                 int* __restrict__ kept, float* __restrict__ kept_mass) {
-    __shared__ TpShared sm;
-    const int b = blockIdx.x, t = threadIdx.x;
-    if (finished && finished[b]) {  // uniform over the workgroup
-        if (t == 0) {
-            tokens[b] = eos_id;
-            if (kept) kept[b] = 0;
-            if (kept_mass) kept_mass[b] = 0.f;
-        }
-        return;
-    }
-    const int per = (V + TP_THREADS - 1) / TP_THREADS;
-    const int i0 = t * per;
-    const int nv = max(0, min(per, V - i0));  // valid tokens of this thread: j < nv
-    const float* row = logits + (size_t)b * ldl;
-    float e[NPT];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        e[j] = j < nv ? row[i0 + j] : -INFINITY;
-        mx = fmaxf(mx, e[j]);
-    }
-    mx = wave_max(mx);
-    if ((t & 63) == 0) sm.red[t >> 6] = mx;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < TP_THREADS / 64; ++w) mx = fmaxf(mx, sm.red[w]);
-    unsigned long long mine = 0;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const float x = expf(e[j] - mx);
-        e[j] = (j < nv && x >= 0.f) ? x : -1.f;
-        mine += tp_q(e[j]);
-    }
-    unsigned long long S;
-    tp_scan(mine, sm.scan, S);
-    // T: the largest mass of the ranks before a kept token
-    unsigned long long T = top_p >= 1.f ? S : (top_p <= 0.f ? 0ull : (unsigned long long)((double)top_p * (double)S));
-    T = min(T, S);
-    // threshold search: after level p, `prefix` = the leading bits of the smallest kept value, `above` = count
-    // and mass (packed) of the tokens whose value lies above every value with that prefix
-    unsigned prefix = 0;
-    unsigned long long above = 0, in_bin = 0;
-#pragma unroll 1
-    for (int level = 0; level < 3; ++level) {
-        const int shift = level == 0 ? 20 : (level == 1 ? 9 : 0);
-        const int bits = level == 2 ? 9 : 11;
-        sm.hist[t] = 0;
-        sm.hist[t + TP_THREADS] = 0;
-        if (t == 0) sm.sel = TP_BINS;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < NPT; ++j) {
-            const float ej = tp_use(e[j]);
-            const unsigned key = __float_as_uint(ej);
-            if (ej >= 0.f && (level == 0 || (key >> (shift + bits)) == prefix))
-                atomicAdd(&sm.hist[(key >> shift) & ((1u << bits) - 1)], (1ull << TP_CNT_SHIFT) | tp_q(ej));
-        }
-        __syncthreads();
-        // thread t owns bins bh > bl, the threads walk the bins downwards: an exclusive scan gives what lies above
-        const int bh = TP_BINS - 1 - 2 * t, bl = bh - 1;
-        const unsigned long long hh = sm.hist[bh], hl = sm.hist[bl];
-        unsigned long long tot;
-        const unsigned long long ah = above + tp_scan(hh + hl, sm.scan, tot), al = ah + hh;
-        // the smallest non-empty bin whose top value still has at most T above it holds the threshold
-        if (hl && (al & TP_MASS_MASK) <= T) atomicMin(&sm.sel, bl);
-        else if (hh && (ah & TP_MASS_MASK) <= T) atomicMin(&sm.sel, bh);
-        __syncthreads();
-        const int sel = sm.sel;
-        if (sel == bh || sel == bl) {
-            sm.pick[0] = sel == bh ? ah : al;
-            sm.pick[1] = sel == bh ? hh : hl;
-        }
-        __syncthreads();
-        above = sm.pick[0];
-        in_bin = sm.pick[1];
-        prefix = (prefix << bits) | (unsigned)sel;
-        __syncthreads();
-    }
-    // prefix = the bit pattern of the smallest kept value v; `in_bin` counts its ties, kept in token order while
-    // the mass before each stays <= T
-    const unsigned vkey = prefix;
-    const unsigned long long G = above & TP_MASS_MASK, qv = tp_q(__uint_as_float(vkey));
-    const unsigned ties = (unsigned)(in_bin >> TP_CNT_SHIFT);
-    const unsigned keep_ties = qv == 0 ? ties : (unsigned)min((unsigned long long)ties, (T - G) / qv + 1);
-    unsigned long long c_eq = 0;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) c_eq += __float_as_uint(tp_use(e[j])) == vkey ? 1u : 0u;
-    unsigned long long tot;
-    unsigned rank = (unsigned)tp_scan(c_eq, sm.scan, tot);  // ties in lower token ids
-    unsigned keepbits_lo = 0, keepbits_hi = 0;
-    mine = 0;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const float ej = tp_use(e[j]);
-        const unsigned key = __float_as_uint(ej);
-        bool k = ej >= 0.f && key > vkey;
-        if (key == vkey) k = rank++ < keep_ties;
-        if (k) {
-            mine += tp_q(ej);
-            if (j < 32) keepbits_lo |= 1u << j;
-            else keepbits_hi |= 1u << (j - 32);
-        }
-    }
-    unsigned long long K;
-    unsigned long long run = tp_scan(mine, sm.scan, K);
-    // the draw: first kept token, in token order, whose running sum reaches u·K
-    // the counter's row and step: the workgroup's own row and the call's step, or (ergm_topp_sample_rows) per row
-    const uint32_t crow = row_ids ? row_ids[b] : (uint32_t)b, cstep = row_steps ? row_steps[b] : step;
-    const uint4 r = philox4x32_10(make_uint4(crow, 0u, 0xE5A3u, cstep), seed_lo, seed_hi);
-    const double u = ((double)r.x + 0.5) * (1.0 / 4294967296.0);
-    unsigned long long target = (unsigned long long)ceil(u * (double)K);
-    target = max(1ull, min(target, K));
-    if (t == 0) sm.sel = V - 1;
-    __syncthreads();
-    bool found = false;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const bool k = j < 32 ? (keepbits_lo >> j) & 1u : (keepbits_hi >> (j - 32)) & 1u;
-        if (k) {
-            run += tp_q(tp_use(e[j]));
-            if (!found && run >= target) {
-                found = true;
-                atomicMin(&sm.sel, i0 + j);
-            }
-        }
-    }
-    __syncthreads();
-    if (t == 0) {
-        const int tok = sm.sel;
-        tokens[b] = tok;
-        if (kept) kept[b] = (int)(above >> TP_CNT_SHIFT) + (int)keep_ties;
-        if (kept_mass) kept_mass[b] = (float)((double)K / (double)S);
-        if (finished && tok == eos_id) finished[b] = 1;
-    }
-}
-
-// ---- sampling with per-row controls (ergm_sample_rows) ---------------------------------------------------
-// NaN, infinite or <= 0 acts as 1
+// The controls of ergm_sample_ctl (ergm_sample_rows).  NaN, infinite or <= 0 acts as 1
 __device__ __forceinline__ float sm_scale(const float* p, int b) {
     const float v = p ? p[b] : 1.f;
     return (v > 0.f && v < INFINITY) ? v : 1.f;
@@ -385,32 +241,35 @@ __device__ __forceinline__ float sm_scale(const float* p, int b) {
 // the repetition penalty on the logit of a token the row has seen
 __device__ __forceinline__ float sm_penalty(float x, float rep) { return x < 0.f ? x * rep : __fdiv_rn(x, rep); }
 
-struct SmShared {
-    TpShared tp;
-    float mx;
-};
-
-// topp_sample_kernel with the controls of ergm_sample_ctl.  The penalty, the eos mask and the temperature act on the
-// registers right behind the load, so the passes below see what the old kernel sees.  The threshold search runs once more, ahead of
-// the mass search and with the packed count as its criterion, for the rows that ask for top-k (uniform over the
-// workgroup); its result is a few uniform values carried across the mass search.
-template <int NPT>
-__global__ __launch_bounds__(TP_THREADS) void sample_rows_kernel(const float* __restrict__ logits, int ldl, int V, float top_p,
-                                                                 ergm_sample_ctl ctl, uint32_t seed_lo, uint32_t seed_hi,
-                                                                 const uint32_t* __restrict__ row_ids,
-                                                                 const uint32_t* __restrict__ row_steps, uint8_t* finished,
-                                                                 int64_t eos_id, int64_t* __restrict__ tokens,
-                                                                 int* __restrict__ kept, float* __restrict__ kept_mass,
-                                                                 float* __restrict__ logprob) {
-    __shared__ SmShared smx;
-    TpShared& sm = smx.tp;
+// The sampler: one workgroup per row; thread t holds the `per` consecutive tokens from t·per in registers.
+// CTL = false is nucleus sampling alone (ergm_topp_sample, ergm_topp_sample_rows): the counter's row and step are
+// row_ids[b] / row_steps[b] where given, else the workgroup's own row and the call's `step`; `ctl` and `logprob` are
+// not read.  CTL = true adds the controls of ergm_sample_ctl (ergm_sample_rows; row_ids and row_steps are given): the
+// penalty, the eos mask and the temperature act on the registers right behind the load, so the passes below see a
+// row as CTL = false sees it.  The threshold search runs once more, ahead of the mass search and with the packed
+// count as its criterion, for the rows that ask for top-k (uniform over the workgroup); its result is a few uniform
+// values carried across the mass search.  Everything CTL adds stands under `if constexpr`, so a row with no control
+// asked of it gives the same bits from either instantiation and CTL = false pays for none of it.  The order of the
+// arguments and of the first statements is measured, not free: with `logprob` and `ctl` last the arguments CTL = false
+// reads keep their kernarg offsets, and the register allocation of both instantiations follows from it (DESIGN.md
+// §12.4).
+template <int NPT, bool CTL>
+__global__ __launch_bounds__(TP_THREADS) void sample_kernel(const float* __restrict__ logits, int ldl, int V, float top_p,
+                                                            uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
+                                                            const uint32_t* __restrict__ row_ids,
+                                                            const uint32_t* __restrict__ row_steps, uint8_t* finished,
+                                                            int64_t eos_id, int64_t* __restrict__ tokens,
+                                                            int* __restrict__ kept, float* __restrict__ kept_mass,
+                                                            float* __restrict__ logprob, ergm_sample_ctl ctl) {
+    __shared__ TpShared sm;
     const int b = blockIdx.x, t = threadIdx.x;
     if (finished && finished[b]) {  // uniform over the workgroup
         if (t == 0) {
             tokens[b] = eos_id;
             if (kept) kept[b] = 0;
             if (kept_mass) kept_mass[b] = 0.f;
-            if (logprob) logprob[b] = 0.f;
+            if constexpr (CTL)
+                if (logprob) logprob[b] = 0.f;
         }
         return;
     }
@@ -418,37 +277,44 @@ __global__ __launch_bounds__(TP_THREADS) void sample_rows_kernel(const float* __
     const int i0 = t * per;
     const int nv = max(0, min(per, V - i0));  // valid tokens of this thread: j < nv
     const float* row = logits + (size_t)b * ldl;
-    uint32_t* seen = ctl.seen ? ctl.seen + (size_t)b * ctl.ld_seen : nullptr;
-    const uint32_t cstep = row_steps[b];
+    // the counter's step: the row's own where given, else the call's; the row's bitmap (CTL)
+    uint32_t cstep = step;
+    uint32_t* seen = nullptr;
+    if constexpr (CTL) {
+        seen = ctl.seen ? ctl.seen + (size_t)b * ctl.ld_seen : nullptr;
+        cstep = row_steps[b];
+    }
     float e[NPT];
 #pragma unroll
     for (int j = 0; j < NPT; ++j) e[j] = j < nv ? row[i0 + j] : -INFINITY;
-    // Steps 1 to 3 of the rule, each a pass of its own over the registers, taken only by the rows that ask for it:
-    // the penalty's and the temperature's conditions are uniform over the workgroup (a factor of 1 changes no bit, so
-    // skipping it is exact), the eos mask is the business of the one thread that holds eos.
-    const float rep = sm_scale(ctl.rep_penalty, b);
-    if (seen && rep != 1.f) {
-        uint32_t word = 0;
+    if constexpr (CTL) {
+        // Steps 1 to 3 of the rule, each a pass of its own over the registers, taken only by the rows that ask for it:
+        // the penalty's and the temperature's conditions are uniform over the workgroup (a factor of 1 changes no bit,
+        // so skipping it is exact), the eos mask is the business of the one thread that holds eos.
+        const float rep = sm_scale(ctl.rep_penalty, b);
+        if (seen && rep != 1.f) {
+            uint32_t word = 0;
 #pragma unroll
-        for (int j = 0; j < NPT; ++j) {
-            const int idx = i0 + j;
-            if (j < nv) {
-                if (j == 0 || (idx & 31) == 0) word = seen[idx >> 5];  // one read per 32 tokens
-                if ((word >> (idx & 31)) & 1u) e[j] = sm_penalty(e[j], rep);
+            for (int j = 0; j < NPT; ++j) {
+                const int idx = i0 + j;
+                if (j < nv) {
+                    if (j == 0 || (idx & 31) == 0) word = seen[idx >> 5];  // one read per 32 tokens
+                    if ((word >> (idx & 31)) & 1u) e[j] = sm_penalty(e[j], rep);
+                }
             }
         }
-    }
-    // while the row is below its minimum length eos is a slot that holds no token, as a NaN logit is: no mass, never
-    // counted
-    if (ctl.min_step && cstep < ctl.min_step[b] && eos_id >= i0 && eos_id < i0 + nv) {
-        const int eos_j = (int)eos_id - i0;
+        // while the row is below its minimum length eos is a slot that holds no token, as a NaN logit is: no mass,
+        // never counted
+        if (ctl.min_step && cstep < ctl.min_step[b] && eos_id >= i0 && eos_id < i0 + nv) {
+            const int eos_j = (int)eos_id - i0;
 #pragma unroll
-        for (int j = 0; j < NPT; ++j) e[j] = j == eos_j ? __builtin_nanf("") : e[j];
-    }
-    const float temp = sm_scale(ctl.temperature, b);
-    if (temp != 1.f) {
+            for (int j = 0; j < NPT; ++j) e[j] = j == eos_j ? __builtin_nanf("") : e[j];
+        }
+        const float temp = sm_scale(ctl.temperature, b);
+        if (temp != 1.f) {
 #pragma unroll
-        for (int j = 0; j < NPT; ++j) e[j] = __fdiv_rn(e[j], temp);
+            for (int j = 0; j < NPT; ++j) e[j] = __fdiv_rn(e[j], temp);
+        }
     }
     float mx = -INFINITY;
 #pragma unroll
@@ -458,38 +324,48 @@ __global__ __launch_bounds__(TP_THREADS) void sample_rows_kernel(const float* __
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < TP_THREADS / 64; ++w) mx = fmaxf(mx, sm.red[w]);
-    if (t == 0) smx.mx = mx;
+    if constexpr (CTL)
+        if (t == 0) sm.mx = mx;
     unsigned long long mine = 0;
 #pragma unroll
     for (int j = 0; j < NPT; ++j) {
         const float x = expf(e[j] - mx);
         e[j] = (j < nv && x >= 0.f) ? x : -1.f;
         const unsigned long long q = tp_q(e[j]);
-        mine += q ? (1ull << TP_CNT_SHIFT) | q : 0ull;  // count << 47 | mass of the tokens with mass
+        if constexpr (CTL) mine += q ? (1ull << TP_CNT_SHIFT) | q : 0ull;  // count << 47 | mass of the tokens with mass
+        else mine += q;
     }
     unsigned long long Sn;
     tp_scan(mine, sm.scan, Sn);
-    const unsigned long long S = Sn & TP_MASS_MASK;
-    const float tp = ctl.top_p ? ctl.top_p[b] : top_p;
-    const int k_raw = ctl.top_k ? ctl.top_k[b] : 0;
-    // top-k is on for 1 <= k < the number of tokens with mass
-    const unsigned k = (k_raw >= 1 && (unsigned long long)k_raw < (Sn >> TP_CNT_SHIFT)) ? (unsigned)k_raw : 0u;
-    // the result of the top-k search (k != 0): the smallest value that remains, what lies above it, its ties that remain
-    unsigned k_key = 0, k_ties = 0;
+    const unsigned long long S = CTL ? Sn & TP_MASS_MASK : Sn;
+    // the row's top_p and top-k, and the result of the top-k search (k != 0): the smallest value that remains, what
+    // lies above it, its ties that remain
+    float tp = top_p;
+    unsigned k = 0, k_key = 0, k_ties = 0;
     unsigned long long k_above = 0;
-    // T: the largest mass of the ranks before a kept token, over the mass S_k that remains under top-k
+    if constexpr (CTL) {
+        if (ctl.top_p) tp = ctl.top_p[b];
+        const int k_raw = ctl.top_k ? ctl.top_k[b] : 0;
+        // top-k is on for 1 <= k < the number of tokens with mass
+        k = (k_raw >= 1 && (unsigned long long)k_raw < (Sn >> TP_CNT_SHIFT)) ? (unsigned)k_raw : 0u;
+    }
+    // threshold search: after level p, `prefix` = the leading bits of the smallest kept value, `above` = count and
+    // mass (packed) of the tokens whose value lies above every value with that prefix.  Pass 1 looks for the smallest
+    // value with at most T of mass above it.  CTL with top-k: pass 0, ahead of it, looks for the smallest value with
+    // fewer than k tokens above it, the same walk over the packed words by count.  CTL = false: the loop's condition
+    // is the constant false, pass 1 is all there is.
     unsigned long long T = 0;
     unsigned prefix = 0;
     unsigned long long above = 0, in_bin = 0;
+    int pass = k ? 0 : 1;
 #pragma unroll 1
-    for (int pass = k ? 0 : 1; pass < 2; ++pass) {
-        // pass 0 looks for the smallest value with fewer than k tokens above it, pass 1 for the smallest with at most
-        // T of mass above it: the same walk over the packed words, by count or by mass
-        const bool by_count = pass == 0;
-        if (!by_count) {
+    do {
+        const bool by_count = CTL && pass == 0;
+        if (!by_count) {  // T over the mass S_k that remains under top-k
             const unsigned long long qk = tp_q(__uint_as_float(k_key));
             const unsigned long long Sk = k ? (k_above & TP_MASS_MASK) + k_ties * qk : S;
-            T = tp >= 1.f ? Sk : (tp > 0.f ? (unsigned long long)((double)tp * (double)Sk) : 0ull);
+            const bool none = CTL ? !(tp > 0.f) : tp <= 0.f;  // a row's own top_p may be a NaN: the top token alone
+            T = tp >= 1.f ? Sk : (none ? 0ull : (unsigned long long)((double)tp * (double)Sk));
             T = min(T, Sk);
         }
         const unsigned long long lim = by_count ? (unsigned long long)(k - 1) : T;
@@ -510,12 +386,14 @@ __global__ __launch_bounds__(TP_THREADS) void sample_rows_kernel(const float* __
                     atomicAdd(&sm.hist[(key >> shift) & ((1u << bits) - 1)], (1ull << TP_CNT_SHIFT) | tp_q(ej));
             }
             __syncthreads();
+            // thread t owns bins bh > bl, the threads walk the bins downwards: an exclusive scan gives what lies above
             const int bh = TP_BINS - 1 - 2 * t, bl = bh - 1;
             const unsigned long long hh = sm.hist[bh], hl = sm.hist[bl];
             unsigned long long tot;
             const unsigned long long ah = above + tp_scan(hh + hl, sm.scan, tot), al = ah + hh;
             const unsigned long long ch = by_count ? ah >> TP_CNT_SHIFT : ah & TP_MASS_MASK;
             const unsigned long long cl = by_count ? al >> TP_CNT_SHIFT : al & TP_MASS_MASK;
+            // the smallest non-empty bin whose top value still has at most `lim` above it holds the threshold
             if (hl && cl <= lim) atomicMin(&sm.sel, bl);
             else if (hh && ch <= lim) atomicMin(&sm.sel, bh);
             __syncthreads();
@@ -534,7 +412,7 @@ __global__ __launch_bounds__(TP_THREADS) void sample_rows_kernel(const float* __
             k_key = prefix, k_above = above;
             k_ties = min((unsigned)(in_bin >> TP_CNT_SHIFT), k - (unsigned)(above >> TP_CNT_SHIFT));
         }
-    }
+    } while (CTL && ++pass < 2);
     // prefix = the bit pattern of the smallest kept value v; `in_bin` counts its ties, kept in token order while
     // the mass before each stays <= T
     unsigned vkey = prefix;
@@ -542,7 +420,8 @@ __global__ __launch_bounds__(TP_THREADS) void sample_rows_kernel(const float* __
     const unsigned ties = (unsigned)(in_bin >> TP_CNT_SHIFT);
     unsigned keep_ties = qv == 0 ? ties : (unsigned)min((unsigned long long)ties, (T - G) / qv + 1);
     // top-p reaches past the ranks that remain under top-k (T = S_k): the top-k cut is the kept set
-    if (k && (unsigned)(above >> TP_CNT_SHIFT) + keep_ties > k) vkey = k_key, above = k_above, keep_ties = k_ties;
+    if constexpr (CTL)
+        if (k && (unsigned)(above >> TP_CNT_SHIFT) + keep_ties > k) vkey = k_key, above = k_above, keep_ties = k_ties;
     unsigned long long c_eq = 0;
 #pragma unroll
     for (int j = 0; j < NPT; ++j) c_eq += __float_as_uint(tp_use(e[j])) == vkey ? 1u : 0u;
@@ -565,7 +444,11 @@ __global__ __launch_bounds__(TP_THREADS) void sample_rows_kernel(const float* __
     unsigned long long K;
     unsigned long long run = tp_scan(mine, sm.scan, K);
     // the draw: first kept token, in token order, whose running sum reaches u·K
-    const uint4 r = philox4x32_10(make_uint4(row_ids[b], 0u, 0xE5A3u, cstep), seed_lo, seed_hi);
+    // the counter's row: per row where given (CTL: always), else the workgroup's own
+    const uint32_t crow = CTL || row_ids ? row_ids[b] : (uint32_t)b;
+    if constexpr (!CTL)
+        if (row_steps) cstep = row_steps[b];
+    const uint4 r = philox4x32_10(make_uint4(crow, 0u, 0xE5A3u, cstep), seed_lo, seed_hi);
     const double u = ((double)r.x + 0.5) * (1.0 / 4294967296.0);
     unsigned long long target = (unsigned long long)ceil(u * (double)K);
     target = max(1ull, min(target, K));
@@ -590,13 +473,15 @@ __global__ __launch_bounds__(TP_THREADS) void sample_rows_kernel(const float* __
         if (kept) kept[b] = (int)(above >> TP_CNT_SHIFT) + (int)keep_ties;
         if (kept_mass) kept_mass[b] = (float)((double)K / (double)S);
         if (finished && tok == eos_id) finished[b] = 1;
-        if (logprob) {  // the token's processed logit once more, from the row and the bitmap as the load saw them
-            float x = row[tok];
-            if (seen && (seen[tok >> 5] >> (tok & 31)) & 1u) x = sm_penalty(x, sm_scale(ctl.rep_penalty, b));
-            x = __fdiv_rn(x, sm_scale(ctl.temperature, b));
-            logprob[b] = (float)((double)(x - smx.mx) - log((double)S * (1.0 / 1073741824.0)));
+        if constexpr (CTL) {
+            if (logprob) {  // the token's processed logit once more, from the row and the bitmap as the load saw them
+                float x = row[tok];
+                if (seen && (seen[tok >> 5] >> (tok & 31)) & 1u) x = sm_penalty(x, sm_scale(ctl.rep_penalty, b));
+                x = __fdiv_rn(x, sm_scale(ctl.temperature, b));
+                logprob[b] = (float)((double)(x - sm.mx) - log((double)S * (1.0 / 1073741824.0)));
+            }
+            if (seen) seen[tok >> 5] |= 1u << (tok & 31);  // this workgroup alone writes the row
         }
-        if (seen) seen[tok >> 5] |= 1u << (tok & 31);  // this workgroup alone writes the row
     }
 }
 
@@ -790,6 +675,27 @@ extern "C" int ergm_embed_rows(const int64_t* ids, const int64_t* tt, const int*
 }
 
 namespace {
+// The one sampler launch, behind each entry point's own argument checks: sample_kernel<NPT, CTL> for the smallest
+// NPT that holds the row.
+template <bool CTL>
+int sample_launch(const char* what, const float* logits, int ldl, int B, int V, float top_p, uint64_t seed, uint32_t step,
+                  const uint32_t* row_ids, const uint32_t* row_steps, void* finished, int64_t eos_id, int64_t* tokens,
+                  int* kept, float* kept_mass, const ergm_sample_ctl& ctl, float* logprob, void* stream) {
+    hipStream_t s = as_stream(stream);
+    auto* fin = reinterpret_cast<uint8_t*>(finished);
+    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
+    const int per = cdiv(V, TP_THREADS);
+#define ERGM_SAMPLE(NPT)                                                                                              \
+    ERGM_LAUNCH((sample_kernel<NPT, CTL>), dim3(B), dim3(TP_THREADS), 0, s, logits, ldl, V, top_p, lo, hi, step, row_ids, \
+                row_steps, fin, eos_id, tokens, kept, kept_mass, logprob, ctl)
+    if (per <= 4) ERGM_SAMPLE(4);
+    else if (per <= 16) ERGM_SAMPLE(16);
+    else ERGM_SAMPLE(52);
+#undef ERGM_SAMPLE
+    return check_launch(what);
+}
+
+// ergm_topp_sample and ergm_topp_sample_rows: nucleus sampling alone
 int topp_launch(const char* what, const float* logits, int ldl, int B, int V, float top_p, uint64_t seed, uint32_t step,
                 const uint32_t* row_ids, const uint32_t* row_steps, void* finished, int64_t eos_id, int64_t* tokens,
                 int* kept, float* kept_mass, void* stream) {
@@ -797,18 +703,8 @@ int topp_launch(const char* what, const float* logits, int ldl, int B, int V, fl
     ERGM_CHECK_ARG(B > 0 && V > 0 && ldl >= V, "%s: bad shape B %d V %d ldl %d", what, B, V, ldl);
     ERGM_CHECK_ARG(top_p == top_p, "%s: top_p is NaN", what);
     if (V > 52 * TP_THREADS) return fail(ERGM_EUNSUPPORTED, "%s: V %d > %d", what, V, 52 * TP_THREADS);
-    hipStream_t s = as_stream(stream);
-    auto* fin = reinterpret_cast<uint8_t*>(finished);
-    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
-    const int per = cdiv(V, TP_THREADS);
-#define ERGM_TOPP(NPT)                                                                                              \
-    ERGM_LAUNCH(topp_sample_kernel<NPT>, dim3(B), dim3(TP_THREADS), 0, s, logits, ldl, V, top_p, lo, hi, step, row_ids, \
-                row_steps, fin, eos_id, tokens, kept, kept_mass)
-    if (per <= 4) ERGM_TOPP(4);
-    else if (per <= 16) ERGM_TOPP(16);
-    else ERGM_TOPP(52);
-#undef ERGM_TOPP
-    return check_launch(what);
+    return sample_launch<false>(what, logits, ldl, B, V, top_p, seed, step, row_ids, row_steps, finished, eos_id, tokens, kept,
+                                kept_mass, ergm_sample_ctl{}, nullptr, stream);
 }
 }  // namespace
 
@@ -839,18 +735,8 @@ extern "C" int ergm_sample_rows(const float* logits, int ldl, int B, int V, floa
     if (ctl) c = *ctl;
     ERGM_CHECK_ARG(!c.seen || c.ld_seen >= cdiv(V, 32), "sample_rows: ld_seen %d < the %d words of a row's bitmap", c.ld_seen,
                    cdiv(V, 32));
-    hipStream_t s = as_stream(stream);
-    auto* fin = reinterpret_cast<uint8_t*>(finished);
-    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
-    const int per = cdiv(V, TP_THREADS);
-#define ERGM_SAMPLE(NPT)                                                                                               \
-    ERGM_LAUNCH(sample_rows_kernel<NPT>, dim3(B), dim3(TP_THREADS), 0, s, logits, ldl, V, top_p, c, lo, hi, row_ids, \
-                row_steps, fin, eos_id, tokens, kept, kept_mass, logprob)
-    if (per <= 4) ERGM_SAMPLE(4);
-    else if (per <= 16) ERGM_SAMPLE(16);
-    else ERGM_SAMPLE(52);
-#undef ERGM_SAMPLE
-    return check_launch("sample_rows");
+    return sample_launch<true>("sample_rows", logits, ldl, B, V, top_p, seed, 0u, row_ids, row_steps, finished, eos_id, tokens,
+                               kept, kept_mass, c, logprob, stream);
 }
 
 extern "C" int ergm_sample_mark(const int64_t* ids, int total, const int* slot, const int* start, const int* len,

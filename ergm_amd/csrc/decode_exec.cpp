@@ -709,44 +709,42 @@ extern "C" int ergm_decode_step_slots(ergm_decode_plan* P, const int64_t* tokens
     return walk(P, w, P->engine, P->d.max_batch, tokens, token_types);
 }
 
-extern "C" int ergm_decode_run_slots(ergm_decode_plan* P, int n, float top_p, uint64_t seed, int64_t eos_id, int64_t sp2_id,
-                                     int64_t* tokens_out, void* stream) {
-    ERGM_TRY(slots_ready(P, "decode_run_slots"));
-    ERGM_CHECK_ARG(n >= 1, "decode_run_slots: n %d < 1", n);
-    ERGM_CHECK_ARG(tokens_out, "decode_run_slots: null tokens_out");
-    ERGM_CHECK_ARG(top_p == top_p, "decode_run_slots: top_p is NaN");
+// n steps over the slots: a token per slot from the logits of the step before, then the step.  ctl null: nucleus
+// sampling alone; else ergm_sample_rows, with the tokens' log-probabilities where asked for.
+static int run_slots(ergm_decode_plan* P, const char* what, int n, float top_p, const ergm_sample_ctl* ctl, uint64_t seed,
+                     int64_t eos_id, int64_t sp2_id, int64_t* tokens_out, float* logprobs_out, void* stream) {
+    ERGM_TRY(slots_ready(P, what));
+    ERGM_CHECK_ARG(n >= 1, "%s: n %d < 1", what, n);
+    ERGM_CHECK_ARG(tokens_out, "%s: null tokens_out", what);
+    ERGM_CHECK_ARG(top_p == top_p, "%s: top_p is NaN", what);
     hipStream_t s = as_stream(stream);
-    const int B = P->d.max_batch;
+    const ergm_decode_dims& d = P->d;
+    const int B = d.max_batch;
     ERGM_TRY(decode_fill_i64(P->tt, sp2_id, B, s));
     for (int i = 0; i < n; ++i) {
         int64_t* tok = tokens_out + (size_t)i * B;
-        ERGM_TRY(ergm_topp_sample_rows(P->logits, P->d.vocab_pad, B, P->d.vocab, top_p, seed, P->row_ids, P->row_steps,
-                                       P->finished, eos_id, tok, nullptr, nullptr, s));
+        if (ctl)
+            ERGM_TRY(ergm_sample_rows(P->logits, d.vocab_pad, B, d.vocab, top_p, ctl, seed, P->row_ids, P->row_steps, P->finished,
+                                      eos_id, tok, nullptr, nullptr, logprobs_out ? logprobs_out + (size_t)i * B : nullptr, s));
+        else
+            ERGM_TRY(ergm_topp_sample_rows(P->logits, d.vocab_pad, B, d.vocab, top_p, seed, P->row_ids, P->row_steps, P->finished,
+                                           eos_id, tok, nullptr, nullptr, s));
         Walk w{false, "decode_step", s};
         ERGM_TRY(walk(P, w, P->engine, B, tok, P->tt));
     }
     return ERGM_OK;
 }
 
+extern "C" int ergm_decode_run_slots(ergm_decode_plan* P, int n, float top_p, uint64_t seed, int64_t eos_id, int64_t sp2_id,
+                                     int64_t* tokens_out, void* stream) {
+    return run_slots(P, "decode_run_slots", n, top_p, nullptr, seed, eos_id, sp2_id, tokens_out, nullptr, stream);
+}
+
 extern "C" int ergm_decode_run_slots_sampled(ergm_decode_plan* P, int n, float top_p, const ergm_sample_ctl* ctl, uint64_t seed,
                                              int64_t eos_id, int64_t sp2_id, int64_t* tokens_out, float* logprobs_out,
                                              void* stream) {
-    ERGM_TRY(slots_ready(P, "decode_run_slots_sampled"));
-    ERGM_CHECK_ARG(n >= 1, "decode_run_slots_sampled: n %d < 1", n);
-    ERGM_CHECK_ARG(tokens_out, "decode_run_slots_sampled: null tokens_out");
-    ERGM_CHECK_ARG(top_p == top_p, "decode_run_slots_sampled: top_p is NaN");
-    hipStream_t s = as_stream(stream);
-    const int B = P->d.max_batch;
-    ERGM_TRY(decode_fill_i64(P->tt, sp2_id, B, s));
-    for (int i = 0; i < n; ++i) {
-        int64_t* tok = tokens_out + (size_t)i * B;
-        ERGM_TRY(ergm_sample_rows(P->logits, P->d.vocab_pad, B, P->d.vocab, top_p, ctl, seed, P->row_ids, P->row_steps,
-                                  P->finished, eos_id, tok, nullptr, nullptr, logprobs_out ? logprobs_out + (size_t)i * B : nullptr,
-                                  s));
-        Walk w{false, "decode_step", s};
-        ERGM_TRY(walk(P, w, P->engine, B, tok, P->tt));
-    }
-    return ERGM_OK;
+    const ergm_sample_ctl none{};  // no control asked for: still ergm_sample_rows, at its defaults
+    return run_slots(P, "decode_run_slots_sampled", n, top_p, ctl ? ctl : &none, seed, eos_id, sp2_id, tokens_out, logprobs_out, stream);
 }
 
 extern "C" int ergm_decode_launches(const ergm_decode_plan* P, int engine) {

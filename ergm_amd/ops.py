@@ -376,17 +376,26 @@ def embed_rows(ids, tt, pos, wte, wpe, out=None):
     return out
 
 
+def _sampler_args(logits, finished, tokens, row_ids=None, row_steps=None):
+    """The samplers' shared checks; returns B and ``tokens`` (allocated if None)."""
+    rows = () if row_ids is None else (row_ids, row_steps)
+    _need_gpu(logits, *rows)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    assert finished is None or finished.dtype == torch.uint8
+    B = logits.shape[0]
+    for t in rows:
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
+    if tokens is None:
+        tokens = torch.empty(B, dtype=torch.int64, device=logits.device)
+    return B, tokens
+
+
 def topp_sample(logits, V: int, top_p: float, seed: int, step: int, eos_id: int, finished=None, tokens=None,
                 kept=None, kept_mass=None):
     """Nucleus sampling of the rows of logits [B, >= V] f32 on the device (ergm_topp_sample); returns ``tokens``
     (int64 [B]).  ``finished`` (uint8 [B]) is read and updated; ``kept`` (int32 [B]) / ``kept_mass`` (f32 [B]) are
     optional diagnostics."""
-    _need_gpu(logits)
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
-    assert finished is None or finished.dtype == torch.uint8
-    B = logits.shape[0]
-    if tokens is None:
-        tokens = torch.empty(B, dtype=torch.int64, device=logits.device)
+    B, tokens = _sampler_args(logits, finished, tokens)
     L.call("ergm_topp_sample", _ptr(logits), logits.stride(0), B, V, float(top_p), seed & (2 ** 64 - 1),
            step & 0xFFFFFFFF, _ptr(finished), eos_id, _ptr(tokens), _ptr(kept), _ptr(kept_mass), _stream(logits.device))
     return tokens
@@ -498,14 +507,7 @@ def topp_sample_rows(logits, V: int, top_p: float, seed: int, row_ids, row_steps
                      tokens=None, kept=None, kept_mass=None):
     """ergm_topp_sample with the Philox counter {row_ids[b], 0, 0xE5A3, row_steps[b]} per row (ergm_topp_sample_rows):
     row_ids / row_steps uint32 [B] on the device, passed as int32 tensors holding the same bits."""
-    _need_gpu(logits, row_ids, row_steps)
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
-    assert finished is None or finished.dtype == torch.uint8
-    B = logits.shape[0]
-    for t in (row_ids, row_steps):
-        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
-    if tokens is None:
-        tokens = torch.empty(B, dtype=torch.int64, device=logits.device)
+    B, tokens = _sampler_args(logits, finished, tokens, row_ids, row_steps)
     L.call("ergm_topp_sample_rows", _ptr(logits), logits.stride(0), B, V, float(top_p), seed & (2 ** 64 - 1), _ptr(row_ids),
            _ptr(row_steps), _ptr(finished), eos_id, _ptr(tokens), _ptr(kept), _ptr(kept_mass), _stream(logits.device))
     return tokens
@@ -530,15 +532,8 @@ def sample_rows(logits, V: int, top_p: float, seed: int, row_ids, row_steps, eos
                 finished=None, tokens=None, kept=None, kept_mass=None, logprob=None):
     """``topp_sample_rows`` with per-row sampling controls (ergm_sample_rows): ``ctl`` from ``sample_ctl`` (None: every
     default, the old sampler's outputs); ``logprob`` (f32 [B], optional) receives the drawn tokens' log-probabilities."""
-    _need_gpu(logits, row_ids, row_steps)
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
-    assert finished is None or finished.dtype == torch.uint8
+    B, tokens = _sampler_args(logits, finished, tokens, row_ids, row_steps)
     assert logprob is None or (logprob.dtype == torch.float32 and logprob.is_contiguous())
-    B = logits.shape[0]
-    for t in (row_ids, row_steps):
-        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
-    if tokens is None:
-        tokens = torch.empty(B, dtype=torch.int64, device=logits.device)
     L.call("ergm_sample_rows", _ptr(logits), logits.stride(0), B, V, float(top_p), None if ctl is None else C.byref(ctl),
            seed & (2 ** 64 - 1), _ptr(row_ids), _ptr(row_steps), _ptr(finished), eos_id, _ptr(tokens), _ptr(kept),
            _ptr(kept_mass), _ptr(logprob), _stream(logits.device))

@@ -166,7 +166,7 @@ ROWS = [
 WANT_KEPT = [3, 1, 2, 1, 0]
 # seeds chosen on the CPU (tests/_topp.py) so that for every live row u·mass lies >= 1e-4·mass from every boundary
 # of the kept tokens' CDF, at top_p = 0.6 and at top_p = 1.0: {V: seed}
-SEEDS = {500: 1, 50257: 1}
+SEEDS = {500: 1, 5000: 1, 50257: 1}
 CHI2_SEED = 5   # the helper's own 4,096 draws with this seed give chi-square 6.31
 
 
@@ -191,7 +191,7 @@ def _sample(gpu, logits, V, top_p, seed, step=0, finished=None):
     return tok.cpu().tolist(), kept.cpu().tolist(), mass.cpu().tolist(), None if fin is None else fin.cpu().tolist()
 
 
-@pytest.mark.parametrize("V", [500, 50257])
+@pytest.mark.parametrize("V", [500, 5000, 50257])
 def test_topp_sample_known_cuts(gpu, V):
     logits = _logits(V)
     seed = SEEDS[V]

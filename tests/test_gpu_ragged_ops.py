@@ -194,7 +194,7 @@ def test_embed_packed_is_bitwise_embed_fwd(gpu):
     assert torch.equal(_bits(h2[st[1]:st[1] + lens[1]]), _bits(hb)) and torch.equal(_bits(cap2), _bits(cap))
 
 
-@pytest.mark.parametrize("V", [500, 50257])
+@pytest.mark.parametrize("V", [500, 5000, 50257])
 def test_topp_sample_rows(gpu, V):
     """At the identity mapping (row_ids = 0 .. B-1, every row_steps = step) all four outputs are ergm_topp_sample's;
     with permuted row_ids, row b draws what the old kernel draws for row row_ids[b] on the same logits."""

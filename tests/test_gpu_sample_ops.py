@@ -13,7 +13,8 @@ from ergm_amd import ops
 pytestmark = pytest.mark.gpu
 
 EOS = 7
-VS = [500, 50257]   # one token per thread, and the widest instantiation
+# one token per thread; 5 per thread with threads 1000-1023 holding none (the middle instantiation); the widest
+VS = [500, 5000, 50257]
 # the rows of tests/test_gpu_decode_ops.py: head probabilities {token: p}, the tail shares the rest evenly
 ROWS = [
     {311: 0.30, 12: 0.20, 140: 0.15, 77: 0.10, 499: 0.05},
@@ -33,7 +34,7 @@ CASES = [
     (ROWS[0], 0.0, dict(), 0.6, [12, 140, 311]),                   # the plain cut beside them
 ]
 # seeds chosen on the CPU (tests/_sample.py) so that every row of CASES has a draw gap >= 1e-4: {V: seed}
-CASE_SEEDS = {500: 1, 50257: 1}
+CASE_SEEDS = {500: 1, 5000: 1, 50257: 1}
 CHI2_SEED = 1       # the helper's own 4,096 draws with this seed give the chi-square in the test's docstring
 MIN_SEED = 1        # with it the helper draws EOS from ROWS[3] at step 0 with a gap >= 1e-4
 
