@@ -460,15 +460,6 @@ __device__ __forceinline__ void vm_ready(const bf16x8& x) {
 }
 __device__ __forceinline__ void vm_ready(float x) { asm volatile("" ::"v"(x)); }
 
-// Ring step: wait until this wave's DMA for the current stage landed (`after` younger stages may stay in
-// flight), finish this wave's LDS reads of the slot about to be refilled, then one workgroup barrier.
-template <int LPS, int NS>
-__device__ __forceinline__ void ring_sync(int after) {
-    wait_stages<LPS, NS - 2>(after);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-}
-
 // The forward's key loop, the one copy every forward kernel runs: zero the lane's Oᵀ column and softmax state, then
 // walk key tiles 0 .. nkt - 1 of K | V (rows < Sk of Kb / Vb) through the NS-stage LDS-DMA ring, fwd_tile on each.
 // q = this lane's query, qw0 = the first query of its wave; mrow = the lane's dropout mask row or null.  What a lane
@@ -678,9 +669,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_qgemm_kernel(AttnArgs a) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int kt = 0; kt < nk; ++kt) {
-            wait_stages<LPS, QG_STAGES - 2>(min(QG_STAGES - 2, nk - 1 - kt));
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
+            ring_sync<LPS, QG_STAGES>(min(QG_STAGES - 2, nk - 1 - kt));
             if (kt + QG_STAGES - 1 < nk) issue(kt + QG_STAGES - 1);
             const char* st = ring + (kt % QG_STAGES) * QG_STAGE;
 #pragma unroll
@@ -1029,9 +1018,7 @@ __global__ __launch_bounds__(512) void attn_bwd_short_kernel(AttnArgs a) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int kt = 0; kt < nk; ++kt) {
-            wait_stages<LPS, AS_GSTAGES - 2>(min(AS_GSTAGES - 2, nk - 1 - kt));
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
+            ring_sync<LPS, AS_GSTAGES>(min(AS_GSTAGES - 2, nk - 1 - kt));
             if (kt + AS_GSTAGES - 1 < nk) issue(kt + AS_GSTAGES - 1);
             const char* st = ring + (kt % AS_GSTAGES) * (AS_GA + AS_GW);
 #pragma unroll

@@ -50,7 +50,7 @@ struct GemmArgs {
     float* colsum_part;    // split-K: per-split partial column sums [z][N] (combined by splitk_reduce_kernel)
     int xcd_split;         // split-K over 8 K slices, one per XCD: grid.x = 8·tiles, slice = blockIdx.x & 7, so
                            // every tile of one K slice shares an XCD's L2 (pipelined kernel only)
-    // MX-fp8 GEMM (gemm_mx_kernel): e8m0 scales of every 32-element K block, A [M][ld_sa], B [N][ld_sb] bytes
+    // MX-fp8 GEMM (gemm_lowp_kernel, MX): e8m0 scales of every 32-element K block, A [M][ld_sa], B [N][ld_sb] bytes
     const uint8_t* a_mx;
     const uint8_t* b_mx;
     int ld_sa, ld_sb;
@@ -216,12 +216,27 @@ struct EpiPre {
 // the staging buffer is (BM/WGM)*(BN+4) floats.  slab != nullptr: raw f32 split-K partials.
 // MF: the accumulator fragments' MFMA shape — 16 (f32x4 per 16x16 fragment: lane l holds rows 4(l>>4)+r of column
 // l&15) or 32 (f32x16 per 32x32 fragment: lane l holds rows (r&3) + 8(r>>2) + 4(l>>5) of column l&31).
-template <int BM, int BN, int WGM, int WGN, int EPI, bool OUT_BF16, int FM, int FN, int NT = 64 * WGM * WGN,
-          bool RS = false, bool QMX = false, int MF = 16, typename AccT = f32x4, bool DYN = false>
-__device__ __forceinline__ void store_tile(const GemmArgs& a, char* lds, AccT (&acc)[FM][FN], int m0, int n0,
-                                           float alpha, float* slab, const EpiPre<EPI, BM, BN, WGM, NT>* pre = nullptr) {
+// O: the options, StoreOpts or a struct derived from it that redefines the ones it sets.
+struct StoreOpts {
+    static constexpr int WAVES = 0;     // waves of the workgroup; 0: the WGM x WGN that hold the accumulators
+    static constexpr bool RS = false;   // fp8 dequantisation by a_scale[m] · b_scale[n]
+    static constexpr bool QMX = false;  // also write the MX copy of the bf16 output (q_out, q_sc)
+    static constexpr int MF = 16;
+    static constexpr bool DYN = false;  // row_map
+};
+template <int MF>
+using acc_t = std::conditional_t<MF == 32, f32x16, f32x4>;
+template <typename O, int WGM, int WGN>
+constexpr int store_threads = 64 * (O::WAVES ? O::WAVES : WGM * WGN);
+
+template <int BM, int BN, int WGM, int WGN, int EPI, bool OUT_BF16, typename O = StoreOpts, int FM, int FN>
+__device__ __forceinline__ void store_tile(const GemmArgs& a, char* lds, acc_t<O::MF> (&acc)[FM][FN], int m0, int n0,
+                                           float alpha, float* slab,
+                                           const EpiPre<EPI, BM, BN, WGM, store_threads<O, WGM, WGN>>* pre = nullptr) {
     // NT: every thread of the workgroup (a warp-specialised kernel adds producer waves, which only
     // help with the copy-out; accumulator fragments come from the WGM x WGN consumer waves)
+    constexpr int NT = store_threads<O, WGM, WGN>, MF = O::MF;
+    constexpr bool RS = O::RS, QMX = O::QMX, DYN = O::DYN;
     constexpr int LD = BN + 4;  // lanes l and l+16 (rows 4 apart) land 16 banks apart
     constexpr int WM = BM / WGM, WN = BN / WGN;
     float* t = reinterpret_cast<float*>(lds);
@@ -347,6 +362,72 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return base + idx;
 }
 
+// ------------------------------------------------------------------------------------------
+// What the kernel bodies below do the same way, written once: the tile of a workgroup, its K slice, the zeroed
+// accumulators, the MFMAs of a 16x16x32 K step and the tail's alpha and slab.  A body uses a helper only where its
+// kernels compile to the same instruction count, opcodes and registers as the spelled-out form (tools/isa_compare.py;
+// DESIGN.md §13 lists which body uses what and why the rest stayed spelled out).  What the bodies do differently on
+// purpose stays with each: which of them leave on id >= nwg (the grouped and the xcd_split grids have spare
+// workgroups; the others' grids are exact), the readfirstlane of the wave index, the DYN exit.
+struct TileAt {
+    int tm, tn, m0, n0;
+};
+// Tile `id` (after the XCD remap) of the tiles_m x tiles_n grid, walked along M (sweep_m) or N.
+template <int BM, int BN>
+__device__ __forceinline__ TileAt tile_at(const GemmArgs& a, int id) {
+    int tm, tn;
+    if (a.sweep_m) { tm = id % a.tiles_m; tn = id / a.tiles_m; }
+    else { tn = id % a.tiles_n; tm = id / a.tiles_n; }
+    return {tm, tn, tm * BM, tn * BN};
+}
+
+struct KSlice {
+    int kbeg, kend, nk;  // [kbeg, kend) and its whole 64-deep steps
+};
+// K slice zs of the split (k_per_split each, the last one to K).  Z: int, or unsigned where zs is blockIdx.z itself;
+// the product and slab_of's 64-bit offset then compile as they did in each body.
+template <typename Z>
+__device__ __forceinline__ KSlice k_slice(const GemmArgs& a, Z zs) {
+    const int kbeg = zs * a.k_per_split;
+    const int kend = min(a.K, kbeg + a.k_per_split);
+    return {kbeg, kend, (kend - kbeg) / GEMM_BK};
+}
+
+template <typename AccT, int FM, int FN>
+__device__ __forceinline__ void zero_acc(AccT (&acc)[FM][FN]) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = AccT{};
+}
+
+// acc[i][j] += fa[i] · fb[j] (v_mfma_f32_16x16x32_bf16); SWAP: operands exchanged, Cᵀ fragments (store_tile_direct).
+template <bool SWAP = false, int FM, int FN>
+__device__ __forceinline__ void mfma_step(const bf16x8 (&fa)[FM], const bf16x8 (&fb)[FN], f32x4 (&acc)[FM][FN]) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+            if constexpr (SWAP) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
+            else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+        }
+}
+
+__device__ __forceinline__ float alpha_of(const GemmArgs& a) {
+    float alpha = a.alpha;
+    if (a.alpha_dev) alpha *= *a.alpha_dev;
+    return alpha;
+}
+// Split-K: slice zs's slab of f32 partials; nullptr without a split.
+template <typename Z>
+__device__ __forceinline__ float* slab_of(const GemmArgs& a, Z zs) {
+    return a.slab ? a.slab + (size_t)zs * a.M * a.N : nullptr;
+}
+
+struct StoreDyn : StoreOpts {
+    static constexpr bool DYN = true;
+};
+
 template <int BM, int BN, bool A_KM, bool B_KN, int EPI, bool OUT_BF16, bool DYN = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(GemmArgs a) {
     if constexpr (DYN) dyn_adjust(a);
@@ -357,17 +438,14 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(GemmArgs a) {
     constexpr int STAGE = A_BYTES + B_BYTES;
 
     const int nwg = a.tiles_m * a.tiles_n;
-    const int id = xcd_remap(blockIdx.x, nwg);
-    int tm, tn;
-    if (a.sweep_m) { tm = id % a.tiles_m; tn = id / a.tiles_m; }
-    else { tn = id % a.tiles_n; tm = id / a.tiles_n; }
-    const int m0 = tm * BM, n0 = tn * BN;
+    const TileAt t = tile_at<BM, BN>(a, xcd_remap(blockIdx.x, nwg));
+    const int m0 = t.m0, n0 = t.n0;
     if constexpr (DYN) {
         if (m0 >= a.M) return;  // a tile past the device-side row count: nothing to compute or store
     }
-    const int kbeg = blockIdx.z * a.k_per_split;
-    const int kend = min(a.K, kbeg + a.k_per_split);
-    const int nk = max(0, kend - kbeg + GEMM_BK - 1) / GEMM_BK;
+    const KSlice k = k_slice(a, blockIdx.z);
+    const int kbeg = k.kbeg, kend = k.kend;
+    const int nk = max(0, kend - kbeg + GEMM_BK - 1) / GEMM_BK;  // any K: the last step may be partial
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int wm = wave >> 1, wn = wave & 1;
@@ -401,11 +479,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(GemmArgs a) {
             for (int i = 0; i < FM; ++i) fa[i] = la.frag(smem + cur * STAGE, wm * WM + i * 16, ks);
 #pragma unroll
             for (int j = 0; j < FN; ++j) fb[j] = lb.frag(smem + cur * STAGE + A_BYTES, wn * WN + j * 16, ks);
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+            mfma_step(fa, fb, acc);
         }
         if (more) {
             la.store(smem + (cur ^ 1) * STAGE);
@@ -416,10 +490,10 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(GemmArgs a) {
 
     float alpha = a.alpha;
     if (a.alpha_dev) alpha *= *a.alpha_dev;
-    float* slab = a.slab ? a.slab + (size_t)blockIdx.z * a.M * a.N : nullptr;
+    float* slab = slab_of(a, blockIdx.z);
     if (a.N % 8 == 0 && (a.slab || a.ldc % 8 == 0)) {
-        store_tile<BM, BN, 2, 2, EPI, OUT_BF16, FM, FN, GEMM_THREADS, false, false, 16, f32x4, DYN>(a, smem, acc, m0, n0,
-                                                                                                 alpha, slab);
+        store_tile<BM, BN, 2, 2, EPI, OUT_BF16, std::conditional_t<DYN, StoreDyn, StoreOpts>>(a, smem, acc, m0, n0, alpha,
+                                                                                              slab);
         return;
     }
     const int lane_ = threadIdx.x & 63, wave_ = threadIdx.x >> 6;
@@ -447,6 +521,11 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(GemmArgs a) {
 // LDS reads are in flight while the pieces queue at the texture unit and the fill overlaps the MFMAs.
 // MF = 32: v_mfma_f32_32x32x16_bf16 on 32x32 fragments (tile images in swizzle family 1, tiles.h frag32), half the
 // MFMA instructions of the 16x16x32 form for the same wave tile; no in-loop bias sums, staged epilogue only.
+template <int MF_, bool DYN_>
+struct PipeStore : StoreOpts {
+    static constexpr int MF = MF_;
+    static constexpr bool DYN = DYN_;
+};
 template <int BM, int BN, int WGM, int WGN, int NS, bool A_KM, bool B_KN, int EPI, bool OUT_BF16, bool DIRECT = false,
           int IL = 0, int MF = 16, bool DYN = false>
 __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& a, const int bid) {
@@ -456,10 +535,8 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& a, const int bid)
     constexpr int WM = BM / WGM, WN = BN / WGN;
     constexpr int FM = WM / MF, FN = WN / MF;
     static_assert(FM >= 1 && FN >= 1 && FM * MF == WM && FN * MF == WN, "wave tile must be a multiple of the MFMA tile");
-    constexpr int A_BYTES = BM * GEMM_BK * 2, B_BYTES = BN * GEMM_BK * 2;
-    constexpr int STAGE = A_BYTES + B_BYTES;
-    constexpr int LPS = GldsTile<BM, A_KM, NW>::PER_WAVE + GldsTile<BN, B_KN, NW>::PER_WAVE;  // vmcnt per stage
-    static_assert(NS >= 2 && NS <= 8 && (NS - 2) * LPS <= 63, "2..8 stages, vmcnt <= 63");
+    using Ring = OperandRing<BM, BN, A_KM, B_KN, NS, NW, SW>;
+    constexpr int A_BYTES = Ring::A_BYTES, STAGE = Ring::STAGE, LPS = Ring::LPS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int nwg = a.tiles_m * a.tiles_n;
@@ -471,38 +548,25 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& a, const int bid)
     const int zs = a.xcd_split ? (bid & 7) + (DYN ? 8 * (int)blockIdx.z : 0) : (int)blockIdx.z;
     const int id = a.xcd_split ? (bid >> 3) : (DYN && a.m_dev) ? bid : xcd_remap(bid, nwg);
     if (id >= nwg) return;
-    int tm, tn;
-    if (a.sweep_m) { tm = id % a.tiles_m; tn = id / a.tiles_m; }
-    else { tn = id % a.tiles_n; tm = id / a.tiles_n; }
-    const int m0 = tm * BM, n0 = tn * BN;
+    const TileAt t = tile_at<BM, BN>(a, id);
+    const int tm = t.tm, m0 = t.m0, n0 = t.n0;
     if constexpr (DYN) {
         if (m0 >= a.M) return;  // a tile past the device-side row count (the whole workgroup leaves, before any barrier)
     }
-    const int kbeg = zs * a.k_per_split;
-    const int kend = min(a.K, kbeg + a.k_per_split);
-    const int nk = DYN ? max(0, kend - kbeg) / GEMM_BK : (kend - kbeg) / GEMM_BK;
+    const KSlice k = k_slice(a, zs);
+    const int kbeg = k.kbeg;
+    const int nk = DYN ? max(0, k.kend - kbeg) / GEMM_BK : k.nk;  // DYN: the device-side K may end before the slice
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave / WGN, wn = wave % WGN;
 
-    using AccT = std::conditional_t<MF == 32, f32x16, f32x4>;
-    AccT acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = AccT{};
+    acc_t<MF> acc[FM][FN];
+    zero_acc(acc);
 
     auto issue_stage = [&](int kt) {
-        char* st = smem + (kt % NS) * STAGE;
-        const int k0 = kbeg + kt * GEMM_BK;
-        GldsTile<BM, A_KM, NW, SW>::issue(st, a.A, a.lda, m0, a.M, k0, wave);
-        GldsTile<BN, B_KN, NW, SW>::issue(st + A_BYTES, a.B, a.ldb, n0, a.N, k0, wave);
+        Ring::issue(smem + (kt % NS) * STAGE, a, m0, n0, kbeg + kt * GEMM_BK, wave);
     };
-    constexpr int PA = GldsTile<BM, A_KM, NW>::PER_WAVE;
-    auto issue_piece = [&](int kt, int p) {  // piece p of this wave's LPS pieces of stage kt (A's first)
-        char* st = smem + (kt % NS) * STAGE;
-        const int k0 = kbeg + kt * GEMM_BK;
-        if (p < PA) GldsTile<BM, A_KM, NW, SW>::issue_piece(st, a.A, a.lda, m0, a.M, k0, wave, p);
-        else GldsTile<BN, B_KN, NW, SW>::issue_piece(st + A_BYTES, a.B, a.ldb, n0, a.N, k0, wave, p - PA);
+    auto issue_piece = [&](int kt, int p) {
+        Ring::issue_piece(smem + (kt % NS) * STAGE, a, m0, n0, kbeg + kt * GEMM_BK, wave, p);
     };
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s)
@@ -525,10 +589,7 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& a, const int bid)
         constexpr bool SUM = decltype(sum_tag)::value;
         for (int kt = 0; kt < nk; ++kt) {
             // stages this wave issued after kt: min(NS-2, nk-1-kt); wait until stage kt has landed
-            const int after = min(NS - 2, nk - 1 - kt);
-            wait_stages<LPS, NS - 2>(after);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of the slot to refill are done
-            __builtin_amdgcn_s_barrier();
+            ring_sync<LPS, NS>(min(NS - 2, nk - 1 - kt));
             const bool refill = kt + NS - 1 < nk;
             if (!IL && refill) issue_stage(kt + NS - 1);
             const char* st = smem + (kt % NS) * STAGE;
@@ -573,15 +634,7 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& a, const int bid)
                         cs[j] = t;
                     }
                 }
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-#pragma unroll
-                    for (int j = 0; j < FN; ++j) {
-                        if constexpr (DIRECT)  // Cᵀ fragments (store_tile_direct)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-                        else
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-                    }
+                mfma_step<DIRECT>(fa, fb, acc);
             }
             }
         }
@@ -592,8 +645,7 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& a, const int bid)
     } else {
         main_loop(std::false_type{});
     }
-    float alpha = a.alpha;
-    if (a.alpha_dev) alpha *= *a.alpha_dev;
+    const float alpha = alpha_of(a);
     if constexpr (CS) {
         if (do_cs) {  // sum the four 16-lane rows (k groups), lane position (column) preserved
             const int lane = threadIdx.x & 63;
@@ -614,9 +666,8 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& a, const int bid)
     if constexpr (DIRECT) {
         store_tile_direct<WGN, EPI, OUT_BF16, FM, FN, WM, WN>(a, acc, m0, n0, alpha);
     } else {
-        float* slab = a.slab ? a.slab + (size_t)zs * a.M * a.N : nullptr;
-        store_tile<BM, BN, WGM, WGN, EPI, OUT_BF16, FM, FN, 64 * WGM * WGN, false, false, MF, AccT, DYN>(a, smem, acc, m0,
-                                                                                                      n0, alpha, slab, &pre);
+        float* slab = slab_of(a, zs);
+        store_tile<BM, BN, WGM, WGN, EPI, OUT_BF16, PipeStore<MF, DYN>>(a, smem, acc, m0, n0, alpha, slab, &pre);
     }
 }
 
@@ -628,6 +679,10 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& a, const int bid)
 // element, fixed order: deterministic), then the staged epilogue with all waves copying out.  An odd K-step count
 // ends with a half-empty pair whose second half re-loads the first half's K step (so every pair issues the same
 // number of pieces and the counted waits stay exact) and group 1 skips it.
+template <int W>
+struct StoreWaves : StoreOpts {
+    static constexpr int WAVES = W;
+};
 template <int BM, int BN, int WGM, int WGN, int NS, bool A_KM, bool B_KN, int EPI, bool OUT_BF16>
 __device__ __forceinline__ void gemm_ks2_body(const GemmArgs& a, const int bid) {
     constexpr int NW = WGM * WGN;  // waves per group
@@ -645,10 +700,8 @@ __device__ __forceinline__ void gemm_ks2_body(const GemmArgs& a, const int bid) 
     const int zs = (int)blockIdx.z;
     const int id = xcd_remap(bid, nwg);
     if (id >= nwg) return;
-    int tm, tn;
-    if (a.sweep_m) { tm = id % a.tiles_m; tn = id / a.tiles_m; }
-    else { tn = id % a.tiles_n; tm = id / a.tiles_n; }
-    const int m0 = tm * BM, n0 = tn * BN;
+    const TileAt t = tile_at<BM, BN>(a, id);
+    const int m0 = t.m0, n0 = t.n0;
     const int kbeg = zs * a.k_per_split;
     const int kend = min(a.K, kbeg + a.k_per_split);
     const int nk = (kend - kbeg) / GEMM_BK;
@@ -727,7 +780,7 @@ __device__ __forceinline__ void gemm_ks2_body(const GemmArgs& a, const int bid) 
     float* slab = a.slab ? a.slab + (size_t)zs * a.M * a.N : nullptr;
     // store_tile opens with a barrier (group 0's reads of `red` are done before the staging reuse); only the
     // group-0 waves hold accumulators, every wave helps with the copy-out
-    store_tile<BM, BN, WGM, WGN, EPI, OUT_BF16, FM, FN, 64 * NT>(a, smem, acc, m0, n0, alpha, slab);
+    store_tile<BM, BN, WGM, WGN, EPI, OUT_BF16, StoreWaves<NT>>(a, smem, acc, m0, n0, alpha, slab);
 }
 
 template <int BM, int BN, int WGM, int WGN, int NS, bool A_KM, bool B_KN, int EPI, bool OUT_BF16>
@@ -788,13 +841,10 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void gemm_ws_kernel(GemmArgs
 
     const int nwg = a.tiles_m * a.tiles_n;
     const int id = xcd_remap(blockIdx.x, nwg);
-    int tm, tn;
-    if (a.sweep_m) { tm = id % a.tiles_m; tn = id / a.tiles_m; }
-    else { tn = id % a.tiles_n; tm = id / a.tiles_n; }
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int kbeg = blockIdx.z * a.k_per_split;
-    const int kend = min(a.K, kbeg + a.k_per_split);
-    const int nk = (kend - kbeg) / GEMM_BK;
+    const TileAt t = tile_at<BM, BN>(a, id);
+    const int m0 = t.m0, n0 = t.n0;
+    const KSlice k = k_slice(a, blockIdx.z);
+    const int kbeg = k.kbeg, nk = k.nk;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool producer = wave >= NC;
     const int pw = wave - NC;
@@ -844,169 +894,95 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void gemm_ws_kernel(GemmArgs
     }
     float alpha = a.alpha;
     if (a.alpha_dev) alpha *= *a.alpha_dev;
-    float* slab = a.slab ? a.slab + (size_t)blockIdx.z * a.M * a.N : nullptr;
+    float* slab = slab_of(a, blockIdx.z);
     // store_tile opens with a barrier: the last stage's reads are done before the staging reuse
-    store_tile<BM, BN, WGM, WGN, EPI, OUT_BF16, FM, FN, 64 * (NC + NP)>(a, smem, acc, m0, n0, alpha, slab);
+    store_tile<BM, BN, WGM, WGN, EPI, OUT_BF16, StoreWaves<NC + NP>>(a, smem, acc, m0, n0, alpha, slab);
 }
 
 // ------------------------------------------------------------------------------------------
-// fp8 (OCP e4m3fn) GEMM for the config-5 forward: A [M][K] and B [N][K] bytes (k contiguous: the
-// activations as produced, the weights stored transposed by ergm_quant_weight_fp8), one
-// v_mfma_scale_f32_16x16x128_f8f6f4 per 16x16 output fragment per 128-deep K step with unit block
-// scales (e8m0 127 = 2^0) — the block-scaled instruction runs e4m3 at twice the bf16 MFMA rate, the
-// unscaled fp8 forms only at the bf16 rate (MI355X_MICROARCH.md, matrix cores).  Dequantisation by the
-// per-row scale of A and per-column scale of B happens once, in the epilogue.
-// A 128-byte K step has the byte layout of the bf16 kernels' 64-element step, so the same LDS-DMA
-// ring (GldsTile on a 2-byte view) and XOR swizzle stage it; lane l reads the 32 bytes of row l&15 at
-// k-offset 32·(l>>4) (two 16-B chunks).
+// fp8 (OCP e4m3fn) GEMMs for the config-5 forward, one kernel (gemm_lowp_kernel) in two forms: A [M][K] and B [N][K]
+// bytes (k contiguous: the activations as produced, the weights stored transposed by ergm_quant_weight_fp8), one
+// v_mfma_scale_f32_16x16x128_f8f6f4 per 16x16 output fragment per 128-deep K step — the block-scaled instruction
+// runs e4m3 at twice the bf16 MFMA rate, the unscaled fp8 forms only at the bf16 rate (MI355X_MICROARCH.md, matrix
+// cores).  A 128-byte K step has the byte layout of the bf16 kernels' 64-element step, so the same LDS-DMA ring
+// (OperandRing on a 2-byte view) and XOR swizzle stage it.
+//   !MX (ergm_gemm_f8): unit block scales (e8m0 127 = 2^0); dequantisation by the per-row scale of A and the
+//   per-column scale of B happens once, in the epilogue (StoreOpts::RS).
+//   MX (ergm_gemm_mx, OCP microscaling): an e8m0 scale per 32-element K block of every row of A (a_mx, pitch ld_sa
+//   rows) and of B (b_mx, pitch ld_sb rows) in the K-step-major layout of common.h mx_sidx, consumed by the MFMA
+//   itself, which applies lane group G's scale byte to K [32G, 32G+32) of the 128-deep step.  The scales of a stage
+//   (4 bytes per row: the 4 blocks of a 128-deep step, 256 contiguous bytes per 64 rows) ride in the same LDS ring
+//   behind the operand tiles (MxScales).  No dequantisation in the epilogue; QMX: the epilogue also writes an MX copy
+//   of its bf16 output (the next fp8 GEMM's A operand).
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-template <int ROWS>
-__device__ __forceinline__ i32x8 frag_f8(const char* lds, int ro) {
+// Operand fragment: lane l reads two 16-B chunks of row l&15, g = l >> 4.  !MX: chunks 2g and 2g+1, the 32 bytes at
+// k-offset 32g.  MX: the block-scaled MFMA reads a lane's 8 dwords as K positions {16g..16g+15} (dwords 0-3) and
+// {64+16g..64+16g+15} (dwords 4-7) and applies the scale of lane group G to K positions [32G, 32G+32) (measured:
+// tools/mx_debug2.py); chunks g and g+4 make those positions the row's memory order, so lane group G's scale byte is
+// that of the 128-deep step's 32-element block G.
+template <bool MX>
+__device__ __forceinline__ i32x8 frag_lowp(const char* lds, int ro) {
     const int lane = threadIdx.x & 63;
     const int row = ro + (lane & 15), g = lane >> 4;
     const char* base = lds + row * 128;
     const int sw = swz_row(row);
-    const uint4 lo = *reinterpret_cast<const uint4*>(base + (((2 * g) ^ sw) << 4));
-    const uint4 hi = *reinterpret_cast<const uint4*>(base + (((2 * g + 1) ^ sw) << 4));
+    const uint4 lo = *reinterpret_cast<const uint4*>(base + (((MX ? g : 2 * g) ^ sw) << 4));
+    const uint4 hi = *reinterpret_cast<const uint4*>(base + (((MX ? g + 4 : 2 * g + 1) ^ sw) << 4));
     return i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
 }
 
-// MX operand fragment: the block-scaled 16x16x128 MFMA reads a lane's 8 dwords as K positions {16g..16g+15} (dwords
-// 0-3) and {64+16g..64+16g+15} (dwords 4-7), g = lane >> 4, and applies the scale of lane group G to K positions
-// [32G, 32G+32) (measured: tools/mx_debug2.py).  Reading 16-B chunks g and g+4 of the row makes those positions
-// the row's memory order, so lane group G's scale byte is that of the 128-deep step's 32-element block G.
-__device__ __forceinline__ i32x8 frag_mx(const char* lds, int ro) {
-    const int lane = threadIdx.x & 63;
-    const int row = ro + (lane & 15), g = lane >> 4;
-    const char* base = lds + row * 128;
-    const int sw = swz_row(row);
-    const uint4 lo = *reinterpret_cast<const uint4*>(base + ((g ^ sw) << 4));
-    const uint4 hi = *reinterpret_cast<const uint4*>(base + (((g + 4) ^ sw) << 4));
-    return i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
-}
+template <bool MX, bool QMX_>
+struct LowpStore : StoreOpts {
+    static constexpr bool RS = !MX, QMX = QMX_;
+};
 
-template <int BM, int BN, int WGM, int WGN, int NS, int EPI, bool OUT_BF16>
-__global__ __launch_bounds__(64 * WGM * WGN) void gemm_f8_kernel(GemmArgs a) {
+template <int BM, int BN, int WGM, int WGN, int NS, int EPI, bool OUT_BF16, bool MX, bool QMX>
+__global__ __launch_bounds__(64 * WGM * WGN) void gemm_lowp_kernel(GemmArgs a) {
+    static_assert(MX || !QMX, "the MX copy of the output: MX form only");
     constexpr int NW = WGM * WGN;
     constexpr int WM = BM / WGM, WN = BN / WGN;
     constexpr int FM = WM / 16, FN = WN / 16;
-    constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128;
-    constexpr int STAGE = A_BYTES + B_BYTES;
-    constexpr int LPS = GldsTile<BM, false, NW>::PER_WAVE + GldsTile<BN, false, NW>::PER_WAVE;
-    static_assert(NS >= 2 && NS <= 8 && (NS - 2) * LPS <= 63, "2..8 stages, vmcnt <= 63");
+    // MX: the stage's scales ride behind its operand tiles, 4 bytes per row, fetched in pieces of 64 rows
+    constexpr int NSP = (BM + BN) / 64;       // scale pieces per stage
+    constexpr int SPW = (NSP + NW - 1) / NW;  // per wave
+    using Ring = OperandRing<BM, BN, false, false, NS, NW, 0, MX ? (BM + BN) * 4 : 0, MX ? SPW : 0>;
+    constexpr int A_BYTES = Ring::A_BYTES, B_BYTES = Ring::B_BYTES, STAGE = Ring::STAGE, LPS = Ring::LPS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int nwg = a.tiles_m * a.tiles_n;
-    const int id = xcd_remap(blockIdx.x, nwg);
-    int tm, tn;
-    if (a.sweep_m) { tm = id % a.tiles_m; tn = id / a.tiles_m; }
-    else { tn = id % a.tiles_n; tm = id / a.tiles_n; }
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int nk = a.K / 128;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave / WGN, wn = wave % WGN;
-    // 2-byte views: a 128-byte K step is "64 elements" of the bf16 staging code
-    const __bf16* A2 = a.A;
-    const __bf16* B2 = a.B;
-    const int lda2 = a.lda / 2, ldb2 = a.ldb / 2;
-
-    f32x4 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    auto issue_stage = [&](int kt) {
-        char* st = smem + (kt % NS) * STAGE;
-        const int k0 = kt * 64;
-        GldsTile<BM, false, NW>::issue(st, A2, lda2, m0, a.M, k0, wave);
-        GldsTile<BN, false, NW>::issue(st + A_BYTES, B2, ldb2, n0, a.N, k0, wave);
-    };
-#pragma unroll
-    for (int s = 0; s < NS - 1; ++s)
-        if (s < nk) issue_stage(s);
-    for (int kt = 0; kt < nk; ++kt) {
-        wait_stages<LPS, NS - 2>(min(NS - 2, nk - 1 - kt));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (kt + NS - 1 < nk) issue_stage(kt + NS - 1);
-        const char* st = smem + (kt % NS) * STAGE;
-        i32x8 fa[FM], fb[FN];
-#pragma unroll
-        for (int i = 0; i < FM; ++i) fa[i] = frag_f8<BM>(st, wm * WM + i * 16);
-#pragma unroll
-        for (int j = 0; j < FN; ++j) fb[j] = frag_f8<BN>(st + A_BYTES, wn * WN + j * 16);
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[i], fb[j], acc[i][j], 0, 0, 0, 127, 0,
-                                                                              127);
-    }
-    float alpha = a.alpha;
-    if (a.alpha_dev) alpha *= *a.alpha_dev;
-    store_tile<BM, BN, WGM, WGN, EPI, OUT_BF16, FM, FN, 64 * NW, true>(a, smem, acc, m0, n0, alpha, nullptr);
-}
-
-// MX-fp8 GEMM (OCP microscaling, config 5's forward): A [M][K] and B [N][K] e4m3 bytes (k contiguous) with an
-// e8m0 scale per 32-element K block of every row of A (a_mx, pitch ld_sa rows) and of B (b_mx, pitch ld_sb rows) in
-// the K-step-major layout of common.h mx_sidx, consumed by the MFMA itself: v_mfma_scale_f32_16x16x128_f8f6f4
-// applies lane group G's scale byte to K [32G, 32G+32) of the 128-deep step (frag_mx).  The scales of a stage
-// (4 bytes per row: the 4 blocks of a 128-deep step, 256 contiguous bytes per 64 rows) ride in the same LDS ring
-// behind the operand tiles, filled by 4-byte-per-lane
-// LDS-DMA (one 64-row piece per wave-instruction; with more waves than pieces the spare waves re-issue piece
-// 0, identical bytes, so every wave issues the same count and the counted waits stay exact).  No
-// per-row / per-column dequantisation in the epilogue; QMX: the epilogue also writes an MX copy of its bf16
-// output (the next fp8 GEMM's A operand).
-template <int BM, int BN, int WGM, int WGN, int NS, int EPI, bool OUT_BF16, bool QMX>
-__global__ __launch_bounds__(64 * WGM * WGN) void gemm_mx_kernel(GemmArgs a) {
-    constexpr int NW = WGM * WGN;
-    constexpr int WM = BM / WGM, WN = BN / WGN;
-    constexpr int FM = WM / 16, FN = WN / 16;
-    constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128;
-    constexpr int SC_BYTES = (BM + BN) * 4;
-    constexpr int STAGE = A_BYTES + B_BYTES + SC_BYTES;
-    constexpr int NSP = (BM + BN) / 64;                // scale pieces per stage (64 rows each)
-    constexpr int SPW = (NSP + NW - 1) / NW;           // per wave
-    constexpr int LPS = GldsTile<BM, false, NW>::PER_WAVE + GldsTile<BN, false, NW>::PER_WAVE + SPW;
-    static_assert(NS >= 2 && NS <= 8 && (NS - 2) * LPS <= 63, "2..8 stages, vmcnt <= 63");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int nwg = a.tiles_m * a.tiles_n;
-    const int id = xcd_remap(blockIdx.x, nwg);
-    int tm, tn;
-    if (a.sweep_m) { tm = id % a.tiles_m; tn = id / a.tiles_m; }
-    else { tn = id % a.tiles_n; tm = id / a.tiles_n; }
-    const int m0 = tm * BM, n0 = tn * BN;
+    const TileAt t = tile_at<BM, BN>(a, xcd_remap(blockIdx.x, nwg));
+    const int m0 = t.m0, n0 = t.n0;
     const int nk = a.K / 128;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int wm = wave / WGN, wn = wave % WGN;
-    const __bf16* A2 = a.A;
-    const __bf16* B2 = a.B;
-    const int lda2 = a.lda / 2, ldb2 = a.ldb / 2;
+
+    // the 2-byte view of the operands: a 128-byte K step is "64 elements" of the bf16 staging code
+    const struct {
+        const __bf16 *A, *B;
+        int lda, ldb, M, N;
+    } v{a.A, a.B, a.lda / 2, a.ldb / 2, a.M, a.N};
 
     f32x4 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     auto issue_stage = [&](int kt) {
         char* st = smem + (kt % NS) * STAGE;
-        const int k0 = kt * 64;
-        GldsTile<BM, false, NW>::issue(st, A2, lda2, m0, a.M, k0, wave);
-        GldsTile<BN, false, NW>::issue(st + A_BYTES, B2, ldb2, n0, a.N, k0, wave);
+        Ring::issue(st, v, m0, n0, kt * 64, wave);
+        if constexpr (MX) {  // 4-byte-per-lane LDS-DMA, one 64-row piece per wave-instruction; with more waves than
+                             // pieces the spare waves re-issue piece 0 (identical bytes), so every wave issues the
+                             // same count and the counted waits stay exact
 #pragma unroll
-        for (int i = 0; i < SPW; ++i) {
-            int p = wave + i * NW;
-            if (p >= NSP) p = 0;  // spare wave: re-issue piece 0 (same bytes, same destination)
-            const bool isb = p * 64 >= BM;
-            const int r = (isb ? p * 64 - BM : p * 64) + lane;
-            const uint8_t* src = isb ? a.b_mx + ((size_t)kt * a.ld_sb + min(n0 + r, a.N - 1)) * 4
-                                     : a.a_mx + ((size_t)kt * a.ld_sa + min(m0 + r, a.M - 1)) * 4;
-            glds4(src, __builtin_amdgcn_readfirstlane(lds_addr_of(st + A_BYTES + B_BYTES + p * 256)));
+            for (int i = 0; i < SPW; ++i) {
+                int p = wave + i * NW;
+                if (p >= NSP) p = 0;  // spare wave: re-issue piece 0 (same bytes, same destination)
+                const bool isb = p * 64 >= BM;
+                const int r = (isb ? p * 64 - BM : p * 64) + lane;
+                const uint8_t* src = isb ? a.b_mx + ((size_t)kt * a.ld_sb + min(n0 + r, a.N - 1)) * 4
+                                         : a.a_mx + ((size_t)kt * a.ld_sa + min(m0 + r, a.M - 1)) * 4;
+                glds4(src, __builtin_amdgcn_readfirstlane(lds_addr_of(st + A_BYTES + B_BYTES + p * 256)));
+            }
         }
     };
 #pragma unroll
@@ -1014,23 +990,23 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_mx_kernel(GemmArgs a) {
         if (s < nk) issue_stage(s);
     const int g = lane >> 4, r16 = lane & 15;
     for (int kt = 0; kt < nk; ++kt) {
-        wait_stages<LPS, NS - 2>(min(NS - 2, nk - 1 - kt));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        ring_sync<LPS, NS>(min(NS - 2, nk - 1 - kt));
         if (kt + NS - 1 < nk) issue_stage(kt + NS - 1);
         const char* st = smem + (kt % NS) * STAGE;
-        const uint32_t* sc = reinterpret_cast<const uint32_t*>(st + A_BYTES + B_BYTES);
+        const uint32_t* sc = reinterpret_cast<const uint32_t*>(st + A_BYTES + B_BYTES);  // MX: the stage's scales
         i32x8 fa[FM], fb[FN];
-        int sa[FM], sb[FN];
+        int sa[FM], sb[FN];  // the lane group's e8m0 scale in bits 0-7; !MX: 127 = 2^0
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
-            fa[i] = frag_mx(st, wm * WM + i * 16);
-            sa[i] = (int)(sc[wm * WM + i * 16 + r16] >> (8 * g));
+            fa[i] = frag_lowp<MX>(st, wm * WM + i * 16);
+            if constexpr (MX) sa[i] = (int)(sc[wm * WM + i * 16 + r16] >> (8 * g));
+            else sa[i] = 127;
         }
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
-            fb[j] = frag_mx(st + A_BYTES, wn * WN + j * 16);
-            sb[j] = (int)(sc[BM + wn * WN + j * 16 + r16] >> (8 * g));
+            fb[j] = frag_lowp<MX>(st + A_BYTES, wn * WN + j * 16);
+            if constexpr (MX) sb[j] = (int)(sc[BM + wn * WN + j * 16 + r16] >> (8 * g));
+            else sb[j] = 127;
         }
 #pragma unroll
         for (int i = 0; i < FM; ++i)
@@ -1041,7 +1017,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_mx_kernel(GemmArgs a) {
     }
     float alpha = a.alpha;
     if (a.alpha_dev) alpha *= *a.alpha_dev;
-    store_tile<BM, BN, WGM, WGN, EPI, OUT_BF16, FM, FN, 64 * NW, false, QMX>(a, smem, acc, m0, n0, alpha, nullptr);
+    store_tile<BM, BN, WGM, WGN, EPI, OUT_BF16, LowpStore<MX, QMX>>(a, smem, acc, m0, n0, alpha, nullptr);
 }
 
 // split-K combine: C = epilogue(alpha * Σ_z slab[z]) in z order (deterministic).
@@ -1049,8 +1025,7 @@ template <int EPI, bool OUT_BF16, bool DYN = false>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs a, int splits) {
     if constexpr (DYN) dyn_adjust(a);  // the slabs hold [z][rows][N] of the device-side row count
     size_t total = (size_t)a.M * a.N;
-    float alpha = a.alpha;
-    if (a.alpha_dev) alpha *= *a.alpha_dev;
+    const float alpha = alpha_of(a);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         float s = 0.f;
         for (int z = 0; z < splits; ++z) s += a.slab[(size_t)z * total + i];
@@ -1565,20 +1540,11 @@ static constexpr F8Cfg kF8Cfgs[] = {
 static constexpr int kNumF8Cfgs = sizeof(kF8Cfgs) / sizeof(kF8Cfgs[0]);
 static thread_local int g_force_f8_cfg = -1;
 
-template <int EPI, bool OB>
-static void launch_f8(const GemmArgs& a, int cfg, hipStream_t s) {
+template <int EPI, bool OB, bool MX, bool QMX = false>
+static void launch_lowp(const GemmArgs& a, int cfg, hipStream_t s) {
     with_cfg<kNumF8Cfgs>(cfg, [&](auto ci) {
         constexpr F8Cfg c = kF8Cfgs[decltype(ci)::value];
-        launch_lds<gemm_f8_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, EPI, OB>, c.lds_bytes(128)>(
-            dim3(a.tiles_m * a.tiles_n), dim3(c.threads()), s, a);
-    });
-}
-
-template <int EPI, bool OB, bool QMX>
-static void launch_mx(const GemmArgs& a, int cfg, hipStream_t s) {
-    with_cfg<kNumF8Cfgs>(cfg, [&](auto ci) {
-        constexpr F8Cfg c = kF8Cfgs[decltype(ci)::value];
-        launch_lds<gemm_mx_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, EPI, OB, QMX>, c.lds_bytes(132)>(
+        launch_lds<gemm_lowp_kernel<c.bm, c.bn, c.wgm, c.wgn, c.ns, EPI, OB, MX, QMX>, c.lds_bytes(MX ? 132 : 128)>(
             dim3(a.tiles_m * a.tiles_n), dim3(c.threads()), s, a);
     });
 }
@@ -1692,19 +1658,19 @@ extern "C" int ergm_gemm_mx(const ergm_gemm_desc* d, const void* A, const void* 
     const bool ob = d->c_dtype == ERGM_BF16;
     switch (e) {
         case ERGM_EPI_NONE:
-            if (ob) launch_mx<ERGM_EPI_NONE, true, false>(a, cfg, s);
-            else launch_mx<ERGM_EPI_NONE, false, false>(a, cfg, s);
+            if (ob) launch_lowp<ERGM_EPI_NONE, true, true, false>(a, cfg, s);
+            else launch_lowp<ERGM_EPI_NONE, false, true, false>(a, cfg, s);
             break;
-        case ERGM_EPI_BIAS: launch_mx<ERGM_EPI_BIAS, true, false>(a, cfg, s); break;
+        case ERGM_EPI_BIAS: launch_lowp<ERGM_EPI_BIAS, true, true, false>(a, cfg, s); break;
         case ERGM_EPI_BIAS_GELU:
-            if (q_out) launch_mx<ERGM_EPI_BIAS_GELU, true, true>(a, cfg, s);
-            else launch_mx<ERGM_EPI_BIAS_GELU, true, false>(a, cfg, s);
+            if (q_out) launch_lowp<ERGM_EPI_BIAS_GELU, true, true, true>(a, cfg, s);
+            else launch_lowp<ERGM_EPI_BIAS_GELU, true, true, false>(a, cfg, s);
             break;
         case ERGM_EPI_GELU_BWD:
-            if (q_out) launch_mx<ERGM_EPI_GELU_BWD, true, true>(a, cfg, s);
-            else launch_mx<ERGM_EPI_GELU_BWD, true, false>(a, cfg, s);
+            if (q_out) launch_lowp<ERGM_EPI_GELU_BWD, true, true, true>(a, cfg, s);
+            else launch_lowp<ERGM_EPI_GELU_BWD, true, true, false>(a, cfg, s);
             break;
-        default: launch_mx<ERGM_EPI_BIAS_RESID, false, false>(a, cfg, s); break;
+        default: launch_lowp<ERGM_EPI_BIAS_RESID, false, true, false>(a, cfg, s); break;
     }
     return check_launch("ergm_gemm_mx");
 }
@@ -1744,12 +1710,12 @@ extern "C" int ergm_gemm_f8(const ergm_gemm_desc* d, const void* A, const float*
     const bool ob = d->c_dtype == ERGM_BF16;
     switch (e) {
         case ERGM_EPI_NONE:
-            if (ob) launch_f8<ERGM_EPI_NONE, true>(a, cfg, s);
-            else launch_f8<ERGM_EPI_NONE, false>(a, cfg, s);
+            if (ob) launch_lowp<ERGM_EPI_NONE, true, false>(a, cfg, s);
+            else launch_lowp<ERGM_EPI_NONE, false, false>(a, cfg, s);
             break;
-        case ERGM_EPI_BIAS: launch_f8<ERGM_EPI_BIAS, true>(a, cfg, s); break;
-        case ERGM_EPI_BIAS_GELU: launch_f8<ERGM_EPI_BIAS_GELU, true>(a, cfg, s); break;
-        default: launch_f8<ERGM_EPI_BIAS_RESID, false>(a, cfg, s); break;
+        case ERGM_EPI_BIAS: launch_lowp<ERGM_EPI_BIAS, true, false>(a, cfg, s); break;
+        case ERGM_EPI_BIAS_GELU: launch_lowp<ERGM_EPI_BIAS_GELU, true, false>(a, cfg, s); break;
+        default: launch_lowp<ERGM_EPI_BIAS_RESID, false, false>(a, cfg, s); break;
     }
     return check_launch("ergm_gemm_f8");
 }

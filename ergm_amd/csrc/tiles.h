@@ -2,7 +2,7 @@
 // XOR-swizzled 16-B chunks, filled either through registers (TileLoader) or by LDS-DMA
 // (global_load_lds_dwordx4, GldsTile) with the swizzle applied on the source address, and read as
 // v_mfma_f32_16x16x32_bf16 operand fragments (ds_read_b128, or ds_read_b64_tr_b16 for the transposed
-// image).  Counted waits: wait_vm / wait_stages.
+// image).  Counted waits: wait_vm / wait_stages / ring_sync; the ring's constants and stage issue: OperandRing.
 #pragma once
 
 #include "common.h"
@@ -152,6 +152,15 @@ __device__ __forceinline__ void wait_stages(int after) {
     }
 }
 
+// Ring step: wait until this wave's DMA for the current stage landed (`after` younger stages may stay in
+// flight), finish this wave's LDS reads of the slot about to be refilled, then one workgroup barrier.
+template <int LPS, int NS>
+__device__ __forceinline__ void ring_sync(int after) {
+    wait_stages<LPS, NS - 2>(after);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+}
+
 // One 16-B-per-lane LDS-DMA: LDS[lds_addr + 16*lane] = *gsrc.  Issued from inline asm so hipcc does
 // not track it (it would otherwise drain vmcnt before every later ds_read); completion is covered by
 // the explicit counted waits.  M0 is saved/set/restored inside the one statement (guide §5.7).
@@ -214,5 +223,36 @@ struct GldsTile {
 // Fragment reader for a staged tile (any wave count): same LDS image and swizzles as TileLoader.
 template <int ROWS, bool TRANS, int SW = 0>
 using FragReader = TileLoader<ROWS, TRANS, SW>;
+
+// The NS-slot LDS ring of a pipelined GEMM: the one home of its stage constants and of "issue K step k0".  The prologue
+// loop and the ring_sync / refill of each step stay in the kernel, whose issue_stage lambda adds what it stages besides.
+// A stage is the A tile (BM rows), the B tile (BN rows) and XBYTES more, which the kernel fills itself with XLPS
+// wave-instructions per wave (the MX scales).  NI waves issue, `wave` is the caller's index among them; SW is the
+// swizzle family of the tile images.  A kernel whose operands are bytes passes its 2-byte view: a 128-byte K step is
+// the 64 elements here.
+template <int BM, int BN, bool A_KM, bool B_KN, int NS, int NI, int SW = 0, int XBYTES = 0, int XLPS = 0>
+struct OperandRing {
+    using TA = GldsTile<BM, A_KM, NI, SW>;
+    using TB = GldsTile<BN, B_KN, NI, SW>;
+    static constexpr int A_BYTES = TA::BYTES, B_BYTES = TB::BYTES;
+    static constexpr int STAGE = A_BYTES + B_BYTES + XBYTES;
+    static constexpr int PA = TA::PER_WAVE;
+    static constexpr int LPS = PA + TB::PER_WAVE + XLPS;  // vmcnt per stage of an issuing wave
+    static_assert(NS >= 2 && NS <= 8 && (NS - 2) * LPS <= 63, "2..8 stages, vmcnt <= 63");
+
+    // The K step at k0 into the stage at st.  a: the kernel's arguments or a view of them (A, lda, M, B, ldb, N),
+    // read where each tile is issued.
+    template <typename Args>
+    __device__ __forceinline__ static void issue(char* st, const Args& a, int m0, int n0, int k0, int wave) {
+        TA::issue(st, a.A, a.lda, m0, a.M, k0, wave);
+        TB::issue(st + A_BYTES, a.B, a.ldb, n0, a.N, k0, wave);
+    }
+    // piece p of this wave's LPS pieces of that K step (A's first)
+    template <typename Args>
+    __device__ __forceinline__ static void issue_piece(char* st, const Args& a, int m0, int n0, int k0, int wave, int p) {
+        if (p < PA) TA::issue_piece(st, a.A, a.lda, m0, a.M, k0, wave, p);
+        else TB::issue_piece(st + A_BYTES, a.B, a.ldb, n0, a.N, k0, wave, p - PA);
+    }
+};
 
 }  // namespace ergm

@@ -57,9 +57,11 @@ def bound(ref, T, K, out_bf16):
     return (U16 if out_bf16 else U32) * ref.abs() + 2.0 * K * U32 * T
 
 
-def check(what, got, ref, T, K, out_bf16, name=None):
-    """got against the fp64 ref: no NaN, every element within bound(), then the relative Frobenius norm the older
-    tests use as a second opinion.  Returns (and records under `name`) the worst err/bound."""
+def check(what, got, ref, T, K, out_bf16, name=None, factor=1.0):
+    """got against the fp64 ref: no NaN, every element within factor * bound(), then the relative Frobenius norm the
+    older tests use as a second opinion (its threshold times the same factor).  Returns (and records under `name`) the worst err/bound (of the bound as
+    derived, whatever the factor).  factor is 1 for every bf16 GEMM; the fp8 / MX cases pass the one measured for the
+    block-scaled MFMA (tests/test_gpu_mx.py LP_FACTOR)."""
     got = got.detach().double().cpu()
     assert got.shape == ref.shape, what
     assert not torch.isnan(got).any().item(), f"{what}: NaN in the result"
@@ -68,13 +70,13 @@ def check(what, got, ref, T, K, out_bf16, name=None):
     ratio = (err / b.clamp_min(1e-300)).max().item() if err.numel() else 0.0
     if name is not None:
         WORST[name] = max(WORST.get(name, 0.0), ratio)
-    bad = err > b
+    bad = err > factor * b
     if bad.any().item():
         i = [int(v[0]) for v in torch.nonzero(bad)[:1].t()]
         raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements past the bound, worst err/bound "
                              f"{ratio:.3g}, first at {i}: got {got[tuple(i)].item()!r} want {ref[tuple(i)].item()!r}")
     rel = ((got - ref).norm() / ref.norm().clamp_min(1e-30)).item()
-    assert rel < (6e-3 if out_bf16 else 1e-5), (what, rel)
+    assert rel < factor * (6e-3 if out_bf16 else 1e-5), (what, rel)
     return ratio
 
 
