@@ -143,6 +143,10 @@ _SIGS = {
     "ergm_decode_step_slots": (i32, [vp, vp, vp, vp]),
     "ergm_decode_run_slots": (i32, [vp, i32, f32, C.c_uint64, i64, i64, vp, vp]),
     "ergm_decode_run_slots_sampled": (i32, [vp, i32, f32, C.POINTER(SampleCtl), C.c_uint64, i64, i64, vp, vp, vp]),
+    "ergm_beam_select_workspace_size": (sz, [i32, i32]),
+    "ergm_beam_select": (i32, [vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
+    "ergm_beam_gather": (i32, [C.POINTER(vp), i32, i64, i64, i32, vp, vp, i32, i32, i32, vp]),
+    "ergm_decode_run_beams": (i32, [vp, i32, i32, i64, i64, vp, vp, vp, vp, sz, vp]),
     "ergm_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "ergm_layernorm_bwd_workspace_size": (sz, [i32, i32]),
     "ergm_layernorm_bwd": (i32, [vp] * 10 + [sz, i32, i32, vp, vp]),

@@ -33,6 +33,8 @@ int decode_slots_admit(const int* slot, const int* n_tok, const int* n_cap, cons
 int decode_slots_advance(int* lens, uint32_t* row_steps, uint8_t* finished, const int* stop_lens, int B, hipStream_t s);
 int decode_slots_extend(const int* slot, const int* past, const int* n_new, const int* max_new, int n_seq, int n_slots,
                         int max_len, int* lens, int* stop_lens, uint8_t* finished, hipStream_t s);
+int beam_select_launches();
+int beam_gather_launches(int n_layer);
 
 // The row buffers a block runs on, for some number of rows R.
 struct Bufs {
@@ -589,6 +591,43 @@ extern "C" int ergm_decode_run(ergm_decode_plan* P, int first, int n, float top_
         }
         ERGM_TRY(ergm_topp_sample(P->logits, P->d.vocab_pad, B, P->d.vocab, top_p, seed, (uint32_t)i, P->finished, eos_id,
                                   tokens_out + (size_t)i * B, nullptr, nullptr, s));
+    }
+    return ERGM_OK;
+}
+
+// n rounds of beam search over the bound rows: select, gather, step (ergm_hip.h has the rule).
+extern "C" int ergm_decode_run_beams(ergm_decode_plan* P, int n, int W, int64_t eos_id, int64_t sp2_id, float* scores,
+                                     int64_t* tokens_out, int* parents_out, void* workspace, size_t ws_bytes, void* stream) {
+    ERGM_CHECK_ARG(P, "decode_run_beams: null plan");
+    ERGM_CHECK_ARG(!P->slots, "decode_run_beams: the plan is bound in slot mode (ergm_decode_bind_slots)");
+    ERGM_CHECK_ARG(n >= 1, "decode_run_beams: n %d < 1", n);
+    ERGM_CHECK_ARG(W >= 1 && W <= 8, "decode_run_beams: W %d outside [1, 8]", W);
+    ERGM_TRY(step_ready(P, n, "decode_run_beams"));
+    ERGM_CHECK_ARG(P->B % W == 0, "decode_run_beams: the %d bound rows are no multiple of W %d", P->B, W);
+    ERGM_CHECK_ARG(W <= P->d.vocab && eos_id >= 0 && eos_id < P->d.vocab, "decode_run_beams: W %d or eos_id %lld outside the vocabulary",
+                   W, (long long)eos_id);
+    ERGM_CHECK_ARG(scores && tokens_out && parents_out && workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+                   "decode_run_beams: null argument or workspace not 8-byte aligned");
+    ERGM_CHECK_ARG(ws_bytes >= ergm_beam_select_workspace_size(P->B, W), "decode_run_beams: workspace %zu < %zu bytes", ws_bytes,
+                   ergm_beam_select_workspace_size(P->B, W));
+    hipStream_t s = as_stream(stream);
+    const ergm_decode_dims& d = P->d;
+    const int B = P->B;
+    const int64_t kv_row = (int64_t)2 * d.n_embd * 2;  // bytes of a K | V row
+    ERGM_TRY(decode_fill_i64(P->tt, sp2_id, B, s));
+    for (int i = 0; i < n; ++i) {
+        int64_t* tok = tokens_out + (size_t)i * B;
+        int* par = parents_out + (size_t)i * B;
+        Walk w{false, "decode_run_beams", s};
+        if (w.on(beam_select_launches()))
+            ERGM_TRY(ergm_beam_select(P->logits, d.vocab_pad, B, W, d.vocab, scores, P->finished, eos_id, par, tok, workspace,
+                                      ws_bytes, s));
+        // n_max bounds every length: the gather's grid covers the rows in use, not the whole cache
+        if (w.on(beam_gather_launches(d.n_layer)))
+            ERGM_TRY(ergm_beam_gather(P->kv.data(), d.n_layer, (int64_t)d.max_len * kv_row, kv_row, (int)kv_row, par, P->lens, B, W,
+                                      P->n_max, s));
+        ERGM_TRY(walk(P, w, P->engine, B, tok, P->tt));
+        P->n_max += 1;
     }
     return ERGM_OK;
 }

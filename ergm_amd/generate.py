@@ -173,7 +173,9 @@ class BatchedGenerator:
 
     ``prefill`` encodes the right-padded prompts with the training kernels (causal attention hides the padding
     from the real rows; the padded rows' K/V land in cache rows >= lens[b], which decode overwrites before it
-    reads them); ``step`` appends one token per sequence; ``generate`` is nucleus sampling of the whole batch.
+    reads them); ``step`` appends one token per sequence; ``generate`` is nucleus sampling of the whole batch;
+    ``beam_search`` (``beam_prefill``, ``beam_round``) is beam search with ``num_beams`` cache rows per prompt, the
+    ranking and the cache reordering on the device (ergm_beam_select, ergm_beam_gather).
 
     ``engine``: "python" (default) drives every kernel of a step from Python; "native" hands the step and the
     sampling loop to the library's decode executor (``ergm_decode_*``), which enqueues the same kernels with the same
@@ -343,10 +345,17 @@ class BatchedGenerator:
     def prefill(self, prompts) -> torch.Tensor:
         """prompts: a list of (input_ids, token_type_ids, caption_ids, imgs, auds) per sequence (1-D or [1, S] id
         tensors of any lengths; imgs / auds may be None).  Returns the next-token logits [B, V] (fp32)."""
+        return self._prefill(prompts, 1)
+
+    def _prefill(self, prompts, W: int) -> torch.Tensor:
+        """The prefill of ``prompts`` into every W-th row: prompt g's cache rows, length and logits land in row g·W,
+        its caption K | V and caption length in all W rows of its group, and the other rows get length 0 and zero
+        logits.  W = 1 is ``prefill``; W > 1 is the state ``beam_prefill`` starts from."""
         self.m.refresh_bf16()
         B = len(prompts)
-        if not 1 <= B <= self.max_batch:
-            raise ValueError(f"{B} prompts for max_batch {self.max_batch}")
+        R = B * W
+        if not 1 <= R <= self.max_batch:
+            raise ValueError(f"{B} prompts" + (f" of {W} beams" if W > 1 else "") + f" for max_batch {self.max_batch}")
         E, H, dev = self.E, self.H, self.dev
         ids_l = [p[0].reshape(-1) for p in prompts]
         cap_l = [p[2].reshape(-1) for p in prompts]
@@ -371,31 +380,38 @@ class BatchedGenerator:
             vis, aud = vis * keep, aud * keep
         h, _ = ops.embed_fwd(ids, tt, ids, wte, wpe, vis, aud)
         _, cap = ops.embed_fwd(cap_ids, None, cap_ids, wte, wpe)
-        self.xkv = [self._gemm(cap, f"transformer.h.{l}.crossattention.c_attn", B * Sc, 2 * E, E,
-                               out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS).view(B, Sc, 2 * E) for l in range(self.L)]
+        xkv = [self._gemm(cap, f"transformer.h.{l}.crossattention.c_attn", B * Sc, 2 * E, E,
+                          out_dtype=torch.bfloat16, epilogue=L.EPI_BIAS).view(B, Sc, 2 * E) for l in range(self.L)]
+        self.xkv = xkv if W == 1 else [t.repeat_interleave(W, 0) for t in xkv]
         n = B * S
 
         def self_attn(l, qkv):
-            self.kv[l][:B, :S].copy_(qkv[:, E:].view(B, S, 2 * E))
+            self.kv[l][:R:W, :S].copy_(qkv[:, E:].view(B, S, 2 * E))
             return ops.attn_fwd(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], B, H, S, S, True)[0]
 
         def cross_attn(l, q):
             a = torch.empty(n, E, dtype=torch.bfloat16, device=dev)
             for b in range(B):   # each sequence over its own caption rows: padded caption rows are never attended
-                kvb = self.xkv[l][b, :clens[b]]
+                kvb = xkv[l][b, :clens[b]]
                 ops.attn_fwd(q[b * S:(b + 1) * S], kvb[:, :E], kvb[:, E:], 1, H, S, clens[b], False,
                              o=a[b * S:(b + 1) * S])
             return a
 
         for l in range(self.L):
             self._block(l, h, n, self_attn, cross_attn)
-        self.B, self.n_max = B, S
-        self.lens[:B] = torch.tensor(lens, dtype=torch.int32, device=dev)
-        self.cap_lens[:B] = torch.tensor(clens, dtype=torch.int32, device=dev)
+        self.B, self.n_max = R, S
+        if W > 1:
+            self.lens[:R] = 0
+        self.lens[:R:W] = torch.tensor(lens, dtype=torch.int32, device=dev)
+        self.cap_lens[:R] = torch.tensor(clens, dtype=torch.int32, device=dev).repeat_interleave(W)
         self.finished.zero_()
-        self._ws = ops.attn_decode_workspace(B, H, max(self.max_len, Sc), dev)
+        self._ws = ops.attn_decode_workspace(R, H, max(self.max_len, Sc), dev)
         last = torch.tensor([b * S + lens[b] - 1 for b in range(B)], device=dev)
         self._logits = self._head(h.index_select(0, last))
+        if W > 1:
+            rows = torch.zeros(R, self._logits.shape[1], dtype=torch.float32, device=dev)
+            rows[::W] = self._logits
+            self._logits = rows
         if self.engine != "python":
             self._bind_plan(Sc)
         return self._logits[:, :self.m.layout.vocab]
@@ -462,6 +478,130 @@ class BatchedGenerator:
             self.step(out[i], tt)
         rows = out[:done].t().cpu().tolist()
         return [r[:r.index(eos_id) + 1] if eos_id in r else r for r in rows]
+
+    # ---- beam search ---------------------------------------------------------------------------------------
+    def _beam_check(self, n_prompts: int, num_beams: int) -> None:
+        if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
+            raise ValueError(f"num_beams {num_beams!r} outside [1, 8]")
+        if num_beams > self.m.layout.vocab:
+            raise ValueError(f"num_beams {num_beams} > the vocabulary")
+        if not 1 <= n_prompts * num_beams <= self.max_batch:
+            raise ValueError(f"{n_prompts} prompts of {num_beams} beams for max_batch {self.max_batch}")
+
+    @torch.no_grad()
+    def beam_prefill(self, prompts, num_beams: int, eos_id: Optional[int] = None, sp2_id: Optional[int] = None):
+        """The state round 0 of a beam search starts from (ergm_hip.h, ergm_decode_run_beams): prompt g in row
+        g·num_beams alone (cache rows, length, logits), its caption K | V in all rows of its group, ``beam_scores``
+        [0, -inf, ...] per group, nothing finished.  ``eos_id`` / ``sp2_id`` are kept for ``beam_round``.  Returns the
+        prompts' next-token logits [G, V]."""
+        self._beam_check(len(prompts), num_beams)
+        W = num_beams
+        self._prefill(prompts, W)
+        R = self.B
+        self.beam_W, self._beam_ids = W, (eos_id, sp2_id)
+        self.beam_scores = torch.full((R,), -math.inf, dtype=torch.float32, device=self.dev)
+        self.beam_scores[::W] = 0.0
+        need = L.load().ergm_beam_select_workspace_size(R, W)
+        self._beam_ws = torch.empty(max(need, 8), dtype=torch.uint8, device=self.dev)
+        return self._logits[::W, :self.m.layout.vocab]
+
+    @torch.no_grad()
+    def beam_round(self, n: int, eos_id: Optional[int] = None, sp2_id: Optional[int] = None):
+        """n rounds of select, gather, step over the rows ``beam_prefill`` left.  Returns ``(tokens, parents)``: n lists
+        over the rows, read back once; the scores and flags stay on the device (``beam_scores``, ``finished``)."""
+        W = getattr(self, "beam_W", None)
+        if W is None or self.B == 0:
+            raise ValueError("beam_round before beam_prefill")
+        eos_id = self._beam_ids[0] if eos_id is None else eos_id
+        sp2_id = self._beam_ids[1] if sp2_id is None else sp2_id
+        if eos_id is None or sp2_id is None:
+            raise ValueError("beam_round needs eos_id and sp2_id (here or at beam_prefill)")
+        V = self.m.layout.vocab
+        if not 0 <= eos_id < V:
+            raise ValueError(f"eos_id {eos_id} outside the vocabulary")
+        if n < 1 or self.n_max + n > self.max_len:
+            raise ValueError(f"{n} round(s) behind {self.n_max} cache rows: outside [1, max_len {self.max_len} - rows]")
+        self._beam_ids = (eos_id, sp2_id)
+        R, dev = self.B, self.dev
+        toks = torch.empty(n, R, dtype=torch.int64, device=dev)
+        pars = torch.empty(n, R, dtype=torch.int32, device=dev)
+        fin = self.finished[:R]
+        if self.engine != "python":
+            p = lambda t: C.c_void_p(t.data_ptr())
+            L.call("ergm_decode_run_beams", self._plan, n, W, eos_id, sp2_id, p(self.beam_scores), p(toks), p(pars),
+                   p(self._beam_ws), self._beam_ws.numel(), self._stream())
+            self.n_max += n
+        else:
+            tt = torch.full((R,), sp2_id, dtype=torch.int64, device=dev)
+            lens = self.lens[:R]
+            for i in range(n):
+                ops.beam_select(self._logits, V, W, self.beam_scores, fin, eos_id, parent=pars[i], token=toks[i],
+                                ws=self._beam_ws)
+                ops.beam_gather(self.kv, pars[i], self.lens, W, max_len=self.n_max)
+                self._logits = self._step_rows(toks[i], tt, lens, self.cap_lens[:R], [t[:R] for t in self.kv], self.xkv)
+                lens.add_((fin == 0).to(torch.int32))
+                self.n_max += 1
+        return toks.cpu().tolist(), pars.cpu().tolist()
+
+    @torch.no_grad()
+    def beam_search(self, prompts, num_beams: int, eos_id: int, sp2_id: int, max_new_tokens: Optional[int] = None,
+                    length_penalty: float = 1.0, num_return: int = 1):
+        """Beam search of ``num_beams`` beams per prompt, the responses typed as speaker 2: the prefill, then chunks of
+        8 rounds with a look at ``finished`` in between, until every row is finished or ``max_new_tokens`` rounds ran.
+        Returns, per prompt, ``num_return`` pairs ``(tokens, sum_logprob)``, best first by
+        ``sum_logprob / len(tokens) ** length_penalty`` (ties by row); each hypothesis ends at its first ``eos_id``
+        (included) or at ``max_new_tokens``.  The device ranks the beams by the raw sum of log-probabilities: the
+        length penalty acts on this final ordering only, not during the search."""
+        self._beam_check(len(prompts), num_beams)
+        if isinstance(num_return, bool) or not isinstance(num_return, int) or not 1 <= num_return <= num_beams:
+            raise ValueError(f"num_return {num_return!r} outside [1, num_beams {num_beams}]")
+        if not 0 <= eos_id < self.m.layout.vocab:
+            raise ValueError(f"eos_id {eos_id} outside the vocabulary")
+        bound = self.max_len - max(int(p[0].numel()) for p in prompts)
+        if max_new_tokens is None:
+            max_new_tokens = bound
+        if max_new_tokens < 1 or max_new_tokens > bound:
+            raise ValueError(f"max_new_tokens {max_new_tokens} outside [1, {bound}] (max_len - the longest prompt)")
+        self.beam_prefill(prompts, num_beams, eos_id, sp2_id)
+        tokens, parents, done = [], [], 0
+        while True:
+            n = min(8, max_new_tokens - done)
+            t, p = self.beam_round(n)
+            tokens += t
+            parents += p
+            done += n
+            if done == max_new_tokens or bool(self.finished[:self.B].all()):
+                break
+        return beam_backtrack(tokens, parents, self.beam_scores.cpu().tolist(), num_beams, eos_id, length_penalty,
+                              num_return)
+
+
+def beam_backtrack(tokens, parents, scores, num_beams: int, eos_id: int, length_penalty: float = 1.0, num_return: int = 1):
+    """The hypotheses of a finished beam search, on the host.  ``tokens`` / ``parents``: one list over the R rows per
+    round (``BatchedGenerator.beam_round``), ``scores`` the rows' final sums of log-probabilities.  The hypothesis of
+    row r is read backwards through ``parents`` and ends at its first ``eos_id`` (included); a row at -inf has none.
+    Returns, per group of ``num_beams`` rows, up to ``num_return`` pairs ``(tokens, score)``, best first by
+    ``score / len(tokens) ** length_penalty``, ties by row."""
+    R = len(scores)
+    if num_beams < 1 or R % num_beams or not 1 <= num_return <= num_beams:
+        raise ValueError(f"{R} rows, num_beams {num_beams}, num_return {num_return}")
+    out = []
+    for g0 in range(0, R, num_beams):
+        hyps = []
+        for r in range(g0, g0 + num_beams):
+            if not scores[r] > -math.inf:
+                continue
+            seq, row = [], r
+            for i in range(len(tokens) - 1, -1, -1):
+                seq.append(int(tokens[i][row]))
+                row = int(parents[i][row])
+            seq.reverse()
+            if eos_id in seq:
+                seq = seq[:seq.index(eos_id) + 1]
+            hyps.append((-(scores[r] / len(seq) ** length_penalty) if seq else math.inf, r, seq, float(scores[r])))
+        hyps.sort(key=lambda h: (h[0], h[1]))
+        out.append([(h[2], h[3]) for h in hyps[:num_return]])
+    return out
 
 
 NO_REQUEST = -1

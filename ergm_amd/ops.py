@@ -558,6 +558,50 @@ def sample_mark(ids, slot, start, length, V: int, seen=None, reset=None, min_new
            _stream(ids.device))
 
 
+def beam_select(logits, V: int, W: int, scores, finished, eos_id: int, parent=None, token=None, ws=None):
+    """One select of beam search over the rows of logits [R, >= V] f32, W consecutive rows per prompt (ergm_beam_select):
+    ``scores`` (f32 [R]) and ``finished`` (uint8 [R]) are read and updated in place; returns ``(parent, token)``, int32 /
+    int64 [R]: the row each row continues and the token it takes.  ``ws``: a uint8 workspace to reuse."""
+    _need_gpu(logits, scores, finished)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    R = logits.shape[0]
+    assert scores.dtype == torch.float32 and finished.dtype == torch.uint8
+    assert scores.is_contiguous() and finished.is_contiguous() and scores.numel() == R and finished.numel() == R
+    dev = logits.device
+    if parent is None:
+        parent = torch.empty(R, dtype=torch.int32, device=dev)
+    if token is None:
+        token = torch.empty(R, dtype=torch.int64, device=dev)
+    assert parent.dtype == torch.int32 and token.dtype == torch.int64 and parent.is_contiguous() and token.is_contiguous()
+    need = L.load().ergm_beam_select_workspace_size(R, W)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    L.call("ergm_beam_select", _ptr(logits), logits.stride(0), R, W, V, _ptr(scores), _ptr(finished), eos_id, _ptr(parent),
+           _ptr(token), _ptr(ws), ws.numel(), _stream(dev))
+    return parent, token
+
+
+def beam_gather(caches, parent, lens, W: int, max_len: Optional[int] = None):
+    """The caches follow the beams (ergm_beam_gather): ``caches`` is a list of per-layer tensors [R, rows, width] with
+    the same strides; for every row with parent[r] != r the cache rows [0, lens[parent[r]]) of every layer go from slot
+    parent[r] to slot r, and lens[r] = lens[parent[r]].  ``max_len``: the host's bound on the lengths (default: rows)."""
+    _need_gpu(parent, lens, *caches)
+    c0 = caches[0]
+    assert parent.dtype == torch.int32 and lens.dtype == torch.int32 and parent.is_contiguous() and lens.is_contiguous()
+    R = parent.numel()
+    for c in caches:
+        assert c.dim() == 3 and c.dtype == c0.dtype and c.shape == c0.shape and c.stride() == c0.stride() and c.stride(2) == 1
+    if c0.shape[0] < R or lens.numel() < R:
+        raise ValueError("beam_gather: fewer cache slots or lengths than rows")
+    es = c0.element_size()
+    rows = c0.shape[1] if max_len is None else max_len
+    if not 1 <= rows <= c0.shape[1]:
+        raise ValueError(f"beam_gather: max_len {rows} outside [1, {c0.shape[1]}]")
+    ptrs = (C.c_void_p * len(caches))(*[c.data_ptr() for c in caches])
+    L.call("ergm_beam_gather", ptrs, len(caches), c0.stride(0) * es, c0.stride(1) * es, c0.shape[2] * es, _ptr(parent),
+           _ptr(lens), R, W, rows, _stream(c0.device))
+
+
 def feat_pool(x: torch.Tensor, lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """Mean over frames of encoder outputs x [B, T, D] (f32 / bf16, any row strides with unit
     last-dim stride) -> [B, D] f32; ``lengths`` [B] int32 limits each sample to its valid frames.

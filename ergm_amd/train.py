@@ -107,7 +107,7 @@ class Trainer:
 
     @torch.no_grad()
     def test(self, loader, top_p: float, eos_id: int, sp2_id: int, seed: int = 0, max_batch: int = 8,
-             max_len: Optional[int] = None, engine: str = "python", sampling=None):
+             max_len: Optional[int] = None, engine: str = "python", sampling=None, num_beams: Optional[int] = None):
         """The reference's ``test()`` (src/main.py:291-335) without the tokenizer: one sampled response for every
         sample of ``loader``, all of them served by one ``ContinuousGenerator`` of ``max_batch`` slots.  A sample's
         prompt is its first n tokens, n = the count of tokens that are not ``eos_id`` (the collate pads with eos), with
@@ -115,8 +115,10 @@ class Trainer:
         loader, so seeded runs repeat.  Returns (hypothesis ids, reference ids = ``labels != -100``, emotion labels, the
         per-batch LM losses of the inference forward ``validation`` runs), lists in loader order.  Decoding the ids
         to text is the caller's.  ``sampling``: one ``SamplingParams`` for every sample (None: plain
-        top-p, the sampler and the launches of before)."""
-        from .generate import ContinuousGenerator
+        top-p, the sampler and the launches of before).  ``num_beams`` = W: the best hypothesis of a beam search of W
+        beams instead of a sample (``BatchedGenerator.beam_search`` in static batches of ``max_batch // W`` prompts;
+        ``top_p``, ``seed`` and ``sampling`` are not used); None is the sampled path, unchanged."""
+        from .generate import BatchedGenerator, ContinuousGenerator
         self.model.eval()
         dev = self.device
         prompts, refs, emos, losses = [], [], [], []
@@ -136,6 +138,17 @@ class Trainer:
             return [], [], [], []
         if max_len is None:
             max_len = self.model.config.n_positions
+        if num_beams is not None:
+            if sampling is not None:
+                raise ValueError("num_beams and sampling exclude each other")
+            per = max_batch // num_beams if num_beams >= 1 else 0
+            if per < 1:
+                raise ValueError(f"num_beams {num_beams} outside [1, max_batch {max_batch}]")
+            beams = BatchedGenerator(self.model, max_batch=max_batch, max_len=max_len, engine=engine)
+            hyps = []
+            for i in range(0, len(prompts), per):
+                hyps += [h[0][0] for h in beams.beam_search(prompts[i:i + per], num_beams, eos_id, sp2_id)]
+            return hyps, refs, emos, [float(x) for x in torch.stack(losses).tolist()]
         gen = ContinuousGenerator(self.model, max_batch=max_batch, max_len=max_len,
                                   cap_max=max(int(p[2].numel()) for p in prompts), engine=engine,
                                   controls=sampling is not None)

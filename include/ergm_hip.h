@@ -28,6 +28,9 @@
  *   ergm_attn_fwd_extend, ergm_rows_to_slots_at, ergm_decode_extend (later additions, same version)
  *   ergm_sample_rows, ergm_sample_mark, ergm_decode_run_slots_sampled (per-request sampling controls, same version)
  *                         the per-token work of nucleus_sampling (src/main.py:253-282), for a batch
+ *   ergm_beam_select, ergm_beam_gather, ergm_decode_run_beams (same version)
+ *                         beam search over the same caches: the cache reordering of _reorder_cache
+ *                         (src/model.py:739-746) and the ranking in front of it, on the device
  *   ergm_linear_rows      Conv1D / lm_head for the few rows of a decode step, with the nn.LayerNorm in front
  *                         of it (src/model.py:298,318,332) computed in the same launch
  *   ergm_decode_*         the token loop of nucleus_sampling (src/main.py:253-282) for a batch, after the
@@ -852,6 +855,53 @@ int ergm_decode_run_slots(ergm_decode_plan* plan, int n, float top_p, uint64_t s
  * symbol (ABI unchanged).                                                                                          */
 int ergm_decode_run_slots_sampled(ergm_decode_plan* plan, int n, float top_p, const ergm_sample_ctl* ctl, uint64_t seed,
                                   int64_t eos_id, int64_t sp2_id, int64_t* tokens_out, float* logprobs_out, void* stream);
+
+/* ---- Beam search (found by symbol, ABI unchanged) ----------------------------------------------------------------
+ * A batch of G prompts with W beams each (1 <= W <= 8, W <= V) occupies R = G·W rows; group g owns rows g·W ..
+ * g·W + W - 1.  A row's state is its score (f32, the sum of the log-probabilities of the tokens the beam has taken),
+ * its finished flag (uint8), its length, its caches and its logits.  One round is select, gather, step.
+ *
+ * Select, per group.  A live beam w (not finished, score above -inf; a NaN score counts as -inf) offers a candidate
+ * (w, j) for every j < V whose logit x_j is finite, with the value
+ *     c = score[w] + ((x_j - max) - ln(S · 2^-30)),
+ * max the row's largest finite logit and S = Σ floor(expf(x - max) · 2^30) its integer mass over the finite logits
+ * (ergm_sample_rows' logprob: the same max, the same exact S; the logarithm is taken in double and rounded to f32 once
+ * per row, the two subtractions and the sum are f32, in that order), so c depends on no summation order.  A finished
+ * beam offers the one candidate (w, eos_id) with c = score[w]; a beam at -inf offers nothing and its logits are not
+ * read.  The W candidates with the largest c are taken, ties to the lower beam, then the lower token.  Slot
+ * assignment depends on the selected set only, not on rank: with the selected candidates ordered by (beam, token)
+ * ascending, the first child of beam w stays in row w of the group, and the remaining children, in that order, fill
+ * the rows of the group's childless beams in ascending row order.  For every row r: parent_out[r] (int32, the global
+ * row index), token_out[r] (int64), scores[r] = c, finished[r] = the parent's flag or token == eos_id.  With fewer than
+ * W candidates the rows left over get score -inf, finished 1, token eos_id, parent r.  scores and finished are updated
+ * in place; the result is the same bits in every run (no float atomics).  workspace: 8-byte aligned, at least
+ * ergm_beam_select_workspace_size(R, W) bytes (0 for a bad R or W).  V <= 53,248; 0 <= eos_id < V.
+ *
+ * Gather.  For every row with parent[r] != r, rows [0, lens[parent[r]]) of every layer's cache go from slot parent[r]
+ * to slot r (slot s of layer l at caches[l] + s·ld_seq, its row i at + i·ld_row, row_bytes each; bytes, multiples of
+ * 16, copied in 16-byte pieces) and lens[r] = lens[parent[r]].  Select's sources keep their own row and its
+ * destinations are childless rows, so no slot is both read and written and the copy is safe in place.  Rows with
+ * parent[r] == r are not touched, nothing at or past the length is written, and a round in which every beam keeps its
+ * row moves no byte.  A parent outside the row's own group, or one that does not keep its own row, counts as self, and
+ * a length is clamped to [0, max_len]: no value makes the kernel follow an index out of a table.  caches: a host array
+ * of n_layer device pointers; one launch covers up to 48 layers.
+ *
+ * ergm_decode_run_beams: n rounds over the state ergm_decode_bind bound with B = R (refused in slot mode): select on
+ * the bound logits into tokens_out[i] / parents_out[i] (device int64 / int32 [n][R]) with scores (device f32 [R]) and
+ * the bound finished flags, gather over the bound self-attention caches and lens, then ergm_decode_step's kernels on
+ * the tokens typed sp2_id (a finished row is stepped on eos without advancing).  Round 0 needs no fan-out: after the
+ * prefill only row g·W of each group holds the prompt (cache rows, length, logits), the scores are [0, -inf, ...], so
+ * all W children come from beam 0 and the gather copies the prompt into the other rows; the caption K | V and cap_lens
+ * are the same in all W rows of a group from the start.  One stream, no events, nothing read back.  workspace: that of
+ * ergm_beam_select for (R, W).  ERGM_EINVAL before any launch for W outside [1, 8], R % W != 0, a plan bound in slot
+ * mode or not bound, and n rounds that would overrun the cache (n_max + n > max_len).                               */
+size_t ergm_beam_select_workspace_size(int R, int W);
+int ergm_beam_select(const float* logits, int ldl, int R, int W, int V, float* scores, uint8_t* finished, int64_t eos_id,
+                     int* parent_out, int64_t* token_out, void* workspace, size_t ws_bytes, void* stream);
+int ergm_beam_gather(void* const* caches, int n_layer, int64_t ld_seq, int64_t ld_row, int row_bytes, const int* parent,
+                     int* lens, int R, int W, int max_len, void* stream);
+int ergm_decode_run_beams(ergm_decode_plan* plan, int n, int W, int64_t eos_id, int64_t sp2_id, float* scores,
+                          int64_t* tokens_out, int* parents_out, void* workspace, size_t ws_bytes, void* stream);
 
 /* Library information and errors. */
 int ergm_version(void);

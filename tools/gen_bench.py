@@ -39,6 +39,12 @@ and ``sample``: the sampler launch alone at B = 32, V = 50,257 on the logits an 
 microseconds per launch in back-to-back windows of 200, the variants alternating inside every repeat: ergm_topp_sample_rows
 (old), ergm_sample_rows with no controls (defaults), top_k=50 only, repetition_penalty=1.2 only (the prompt's ids seen),
 and everything (top_k=50, temperature=0.8, repetition_penalty=1.2).
+Beam search, ``--beams W`` (W = 4 and W = 1 are recorded): G·W = 32 rows, 64 + 64 tokens, per engine the
+milliseconds of one beam_search call beside one generate() call at B = 32 (alternating in one process; generate() and
+everything under it are the parent commit's code, which the feature does not touch), the cache bytes the gather moved
+per round, and the launches of a round alone in back-to-back windows of 200, alternating: select, the sampler launch
+(ergm_topp_sample_rows), the gather of round 0 (W - 1 of W rows move) and a gather in which every beam keeps its row.
+The whole runs in fresh child processes with ERGM_BEAM_SELECT=two and =one, alternating twice.
 Without --case the tool runs every case in turn, each in a fresh child process under its own timeout, one at a
 time, and stops at the first that fails.  --cases a,b,c runs those cases in that
 order (e.g. b32,n32,f32,b32,n32,f32 to alternate engines on one box).  For the kernel-time split of one engine:
@@ -299,6 +305,89 @@ def _turns():
         print(json.dumps(row), flush=True)
 
 
+BEAM_EOS = 50258   # a special token the random model's beams do not reach: every search runs to the bound
+
+
+def _beams(W):
+    """One child of --beams W: beam_search against generate() per engine, and the launches of a round alone."""
+    import torch
+    from ergm_amd import ops
+    from ergm_amd.generate import BatchedGenerator
+    R, N = 32, 200
+    dev, model, prompts, _ = _setup_requests(R)
+    G = R // W
+    mode = os.environ.get("ERGM_BEAM_SELECT", "two")
+    kv_row = 2 * model.config.n_embd * 2
+    for engine in ENGINES.values():
+        gen_b = BatchedGenerator(model, max_batch=R, max_len=PROMPT + NEW, engine=engine)
+        gen_p = BatchedGenerator(model, max_batch=R, max_len=PROMPT + NEW, engine=engine)
+
+        def beam():
+            out = gen_b.beam_search(prompts[:G], W, BEAM_EOS, SP2, max_new_tokens=NEW)
+            assert all(len(h[0][0]) == NEW for h in out)
+
+        def plain():   # the parent commit's call: generate() and everything under it are unchanged by this feature
+            out = gen_p.generate(prompts, top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2, seed=7, max_new_tokens=NEW)
+            assert all(len(r) == NEW for r in out)
+        ms = {"beam": [], "plain": []}
+        for rep in range(REPEATS + 1):   # alternating; the first of each is the warm-up
+            for name, fn in (("beam", beam), ("plain", plain)):
+                t = _event_ms(fn)
+                if rep:
+                    ms[name].append(t)
+        # the cache bytes the gather moved: a row that changed parents copies the rows its parent held
+        gen_b.beam_prefill(prompts[:G], W, BEAM_EOS, SP2)
+        _, parents = gen_b.beam_round(NEW)
+        moved = [sum(1 for r, p in enumerate(par) if p != r) * (PROMPT + i) * kv_row * model.config.n_layer
+                 for i, par in enumerate(parents)]
+        print(json.dumps({"case": "beams", "select": mode, "engine": engine, "W": W, "G": G, "new_tokens": NEW,
+                          "beam_ms_median": round(statistics.median(ms["beam"]), 2), "beam_ms_all": [round(x, 2) for x in ms["beam"]],
+                          "generate_ms_median": round(statistics.median(ms["plain"]), 2),
+                          "generate_ms_all": [round(x, 2) for x in ms["plain"]],
+                          "gather_bytes_round0": moved[0], "gather_bytes_per_round_mean_later": round(sum(moved[1:]) / (NEW - 1)),
+                          "rows_moved_per_round_mean_later": round(sum(sum(1 for r, p in enumerate(par) if p != r)
+                                                                       for par in parents[1:]) / (NEW - 1), 2)}), flush=True)
+    # the launches alone, on the state a search holds after its first round (every row live, 65 cache rows)
+    gen = BatchedGenerator(model, max_batch=R, max_len=PROMPT + NEW, engine="native")
+    gen.beam_prefill(prompts[:G], W, BEAM_EOS, SP2)
+    gen.beam_round(1)
+    logits, V = gen._logits, model.layout.vocab
+    scores0, sc = gen.beam_scores.clone(), gen.beam_scores.clone()
+    fin = torch.zeros(R, dtype=torch.uint8, device=dev)
+    par, tok = torch.empty(R, dtype=torch.int32, device=dev), torch.empty(R, dtype=torch.int64, device=dev)
+    rid, steps = torch.arange(R, dtype=torch.int32, device=dev), torch.zeros(R, dtype=torch.int32, device=dev)
+    fan = torch.arange(R, dtype=torch.int32, device=dev) // W * W            # round 0: W - 1 of W rows move
+    keep = torch.arange(R, dtype=torch.int32, device=dev)                    # every beam keeps its row
+    lens = gen.lens.clone()
+
+    def select():
+        sc.copy_(scores0), fin.zero_()
+        for _ in range(N):
+            ops.beam_select(logits, V, W, sc, fin, BEAM_EOS, parent=par, token=tok, ws=gen._beam_ws)
+
+    def sampler():
+        for _ in range(N):
+            ops.topp_sample_rows(logits, V, TOP_P, 7, rid, steps, NO_EOS, tokens=tok)
+
+    def gather(p):
+        def run():
+            for _ in range(N):
+                ops.beam_gather(gen.kv, p, lens, W, max_len=gen.n_max)
+        return run
+    fns = {"select": select, "sampler": sampler, "gather_fan_out": gather(fan), "gather_none": gather(keep)}
+    us = {n: [] for n in fns}
+    for rep in range(REPEATS + 1):
+        for n, fn in fns.items():
+            t = _event_ms(fn) / N * 1e3
+            if rep:
+                us[n].append(t)
+    fan_bytes = int((fan != keep).sum()) * int(lens[0]) * kv_row * model.config.n_layer
+    for n in fns:
+        print(json.dumps({"case": "beams", "select": mode, "launch": n, "W": W, "R": R, "V": V,
+                          "us_per_call": round(statistics.median(us[n]), 2), "us_all": [round(x, 2) for x in us[n]],
+                          **({"bytes": fan_bytes, "cache_rows": int(lens[0])} if n == "gather_fan_out" else {})}), flush=True)
+
+
 def _attention():
     import torch
     from ergm_amd import ops
@@ -329,6 +418,18 @@ def _attention():
 
 
 def main():
+    if "--beams" in sys.argv:
+        W = int(sys.argv[sys.argv.index("--beams") + 1])
+        if not 1 <= W <= 8 or 32 % W:
+            raise SystemExit("--beams takes 1, 2, 4 or 8")
+        if "--child" in sys.argv:
+            return _beams(W)
+        for mode in ("two", "one", "two", "one"):   # the two forms of select, alternating, a fresh process each
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--beams", str(W), "--child"], timeout=420,
+                               env={**os.environ, "ERGM_BEAM_SELECT": mode})
+            if r.returncode != 0:
+                raise SystemExit(f"--beams {W} (select {mode}) failed with status {r.returncode}: stopping")
+        return
     if "--case" in sys.argv:
         case = sys.argv[sys.argv.index("--case") + 1]
         if case not in CASES:
