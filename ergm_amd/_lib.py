@@ -150,6 +150,8 @@ _SIGS = {
     "ergm_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "ergm_layernorm_bwd_workspace_size": (sz, [i32, i32]),
     "ergm_layernorm_bwd": (i32, [vp] * 10 + [sz, i32, i32, vp, vp]),
+    "ergm_layernorm_fwd_ld": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp]),
+    "ergm_layernorm_bwd_ex": (i32, [vp, i32] + [vp] * 9 + [sz, i32, i32, vp, i32, vp]),
     "ergm_dropout_mask": (i32, [vp, i32, i32, vp, vp]),
     "ergm_dropout_apply": (i32, [vp, vp, i32, i32, i32, vp]),
     "ergm_colsum_workspace_size": (sz, [i32, i32]),

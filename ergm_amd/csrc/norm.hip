@@ -497,15 +497,36 @@ extern "C" int ergm_layernorm_bwd(const float* dy, const float* x, const float* 
                                   const float* gamma, float* dres, void* dres_bf16, float* dgamma, float* dbeta,
                                   void* ws, size_t ws_bytes, int rows, int E, const ergm_dropout* dropout,
                                   void* stream) {
+    return ergm_layernorm_bwd_ex(dy, ERGM_F32, x, mean, rstd, gamma, dres, dres_bf16, dgamma, dbeta, ws, ws_bytes, rows, E,
+                                 dropout, 0, stream);
+}
+
+// The forms the training step runs that ergm_layernorm_fwd / ergm_layernorm_bwd cannot reach: a padded output row
+// (ldy > E), bf16 dy, and the final residual gradient itself taken through the dropout (drop_res, no bf16 copy).
+extern "C" int ergm_layernorm_fwd_ld(const float* x, const float* gamma, const float* beta, void* y, int ldy, float* mean,
+                                     float* rstd, int rows, int E, float eps, void* stream) {
+    return layernorm_fwd_ld(x, gamma, beta, y, ldy, mean, rstd, rows, E, eps, as_stream(stream), nullptr, 0, nullptr,
+                            nullptr, 0);
+}
+
+extern "C" int ergm_layernorm_bwd_ex(const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd,
+                                     const float* gamma, float* dres, void* dres_bf16, float* dgamma, float* dbeta,
+                                     void* ws, size_t ws_bytes, int rows, int E, const ergm_dropout* dropout,
+                                     int drop_res, void* stream) {
     ERGM_CHECK_ARG(dgamma && dbeta, "layernorm_bwd: null argument");
+    ERGM_CHECK_ARG(dy_dtype == ERGM_F32 || dy_dtype == ERGM_BF16, "layernorm_bwd: bad dy dtype");
+    ERGM_CHECK_ARG(drop_res == 0 || drop_res == 1, "layernorm_bwd: drop_res is 0 or 1");
+    // the step passes drop_res only for the embedding slot, which has no bf16 consumer (model.cpp ln_bwd_rows)
+    ERGM_CHECK_ARG(!(drop_res && dres_bf16), "layernorm_bwd: drop_res goes with a null dres_bf16");
+    ERGM_CHECK_ARG(rows > 0 && E > 0 && E % 4 == 0 && E <= 1024, "layernorm_bwd: unsupported E=%d", E);
     ERGM_TRY(check_dropout(dropout));
     ERGM_CHECK_ARG(ws && ws_bytes >= ergm_layernorm_bwd_workspace_size(rows, E), "layernorm_bwd: workspace too small");
     const int nb = ln_bwd_nparts(rows);
     float* pg = reinterpret_cast<float*>(ws);
     float* pb = pg + (size_t)nb * E;
     hipStream_t s = as_stream(stream);
-    ERGM_TRY(layernorm_bwd_main(dy, 0, x, mean, rstd, gamma, dres, dres_bf16, pg, pb, rows, E, s, drop_site_of(dropout, E), 0,
-                                 nullptr, nullptr, 0));
+    ERGM_TRY(layernorm_bwd_main(dy, dy_dtype == ERGM_BF16, x, mean, rstd, gamma, dres, dres_bf16, pg, pb, rows, E, s,
+                                 drop_site_of(dropout, E), drop_res, nullptr, nullptr, 0));
     return layernorm_param_reduce(pg, pb, rows, E, dgamma, dbeta, s);
 }
 

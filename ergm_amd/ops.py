@@ -307,6 +307,40 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dres, dropout: Optional[L.Dropout] =
     return dres, db, dg, dbe
 
 
+def layernorm_fwd_ld(x, gamma, beta, y, eps=1e-5, mean=None, rstd=None):
+    """ergm_layernorm_fwd_ld: ``y`` is a bf16 [rows, E] view whose row stride may exceed E (the pad columns are not
+    written).  Returns (y, mean, rstd)."""
+    _need_gpu(x, gamma, beta, y)
+    rows, E = x.shape
+    if y.dtype != torch.bfloat16 or y.shape != (rows, E) or y.stride(1) != 1:
+        raise ValueError("layernorm_fwd_ld: y is a bf16 [rows, E] view with unit column stride")
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device) if mean is None else mean
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if rstd is None else rstd
+    L.call("ergm_layernorm_fwd_ld", _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), y.stride(0), _ptr(mean), _ptr(rstd), rows,
+           E, eps, _stream(x.device))
+    return y, mean, rstd
+
+
+def layernorm_bwd_ex(dy, x, mean, rstd, gamma, dres, dres_bf16=None, dgamma=None, dbeta=None,
+                     dropout: Optional[L.Dropout] = None, drop_res: bool = False):
+    """ergm_layernorm_bwd_ex: ``dy`` f32 or bf16 [rows, E]; dres += LN_bwd(dy) in place, with ``drop_res`` the sum
+    itself through ``dropout`` (then ``dres_bf16`` is None); ``dres_bf16`` (bf16 [rows, E] or None) as
+    layernorm_bwd's.  Returns (dres, dres_bf16, dgamma, dbeta)."""
+    _need_gpu(dy, x, mean, rstd, gamma, dres)
+    rows, E = x.shape
+    if dy.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("layernorm_bwd_ex: dy is f32 or bf16")
+    lib = L.load()
+    wsb = lib.ergm_layernorm_bwd_workspace_size(rows, E)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=x.device)
+    dgamma = torch.empty(E, dtype=torch.float32, device=x.device) if dgamma is None else dgamma
+    dbeta = torch.empty(E, dtype=torch.float32, device=x.device) if dbeta is None else dbeta
+    L.call("ergm_layernorm_bwd_ex", _ptr(dy), L.BF16 if dy.dtype == torch.bfloat16 else L.F32, _ptr(x), _ptr(mean),
+           _ptr(rstd), _ptr(gamma), _ptr(dres), _ptr(dres_bf16), _ptr(dgamma), _ptr(dbeta), _ptr(ws), wsb, rows, E,
+           _dp(dropout), int(bool(drop_res)), _stream(x.device))
+    return dres, dres_bf16, dgamma, dbeta
+
+
 def colsum(X, out=None, accumulate=False):
     _need_gpu(X)
     rows, cols = X.shape

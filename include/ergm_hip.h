@@ -339,6 +339,19 @@ int ergm_layernorm_bwd(const float* dy, const float* x, const float* mean, const
                        void* workspace, size_t ws_bytes, int rows, int E, const ergm_dropout* dropout,
                        void* stream);
 
+/* The forms of the two calls above that the training step runs.  ergm_layernorm_fwd_ld: y has rows of ldy >= E bf16
+ * (ldy % 4 == 0; the columns past E are not written).  ergm_layernorm_bwd_ex: dy is f32 (ERGM_F32) or bf16 (ERGM_BF16,
+ * the block LayerNorms' form); dres_bf16 may be NULL; drop_res = 1 (dres_bf16 NULL: the step uses it for the
+ * embedding slot only, which has no bf16 consumer) takes the updated dres itself through `dropout`:
+ * dres = (dres + LN_bwd(dy))·keep/(1-p).  With ERGM_F32, drop_res = 0 and dres_bf16 given it is ergm_layernorm_bwd
+ * bit for bit.                                                                                   */
+int ergm_layernorm_fwd_ld(const float* x, const float* gamma, const float* beta, void* y, int ldy, float* mean,
+                          float* rstd, int rows, int E, float eps, void* stream);
+int ergm_layernorm_bwd_ex(const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd,
+                          const float* gamma, float* dres, void* dres_bf16, float* dgamma, float* dbeta,
+                          void* workspace, size_t ws_bytes, int rows, int E, const ergm_dropout* dropout,
+                          int drop_res, void* stream);
+
 /* Column sums of a row-major matrix (bias gradients, wpe gradient): out[c] (=|+=) Σ_r X[r][c]. */
 size_t ergm_colsum_workspace_size(int rows, int cols);
 int ergm_colsum(const void* X, int x_dtype, int rows, int cols, int ldx, float* out, int accumulate,
