@@ -124,6 +124,8 @@ _SIGS = {
     "ergm_embed_packed": (i32, [vp] * 12 + [i32] * 5 + [vp, vp, i32, i32, i32, i32, vp]),
     "ergm_attn_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp] + [i32] * 13 + [vp, vp, vp]),
     "ergm_linear_rows": (i32, [C.POINTER(LinearRowsDesc), vp, vp, vp, vp]),
+    "ergm_lm_score_workspace_size": (sz, [i32, i32, i32]),
+    "ergm_lm_score": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "ergm_decode_workspace_size": (sz, [C.POINTER(DecodeDims)]),
     "ergm_decode_create": (i32, [C.POINTER(DecodeDims), C.POINTER(ModelParams), vp, sz, C.POINTER(vp)]),
     "ergm_decode_destroy": (i32, [vp]),
@@ -140,6 +142,9 @@ _SIGS = {
     "ergm_decode_extend": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, vp,
                                  vp, vp, vp, sz, vp]),
     "ergm_decode_extend_launches": (i32, [vp, i32, i32]),
+    "ergm_decode_score_workspace_size": (sz, [C.POINTER(DecodeDims), i32, i32]),
+    "ergm_decode_score": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "ergm_decode_score_launches": (i32, [vp, i32, i32, i32]),
     "ergm_decode_step_slots": (i32, [vp, vp, vp, vp]),
     "ergm_decode_run_slots": (i32, [vp, i32, f32, C.c_uint64, i64, i64, vp, vp]),
     "ergm_decode_run_slots_sampled": (i32, [vp, i32, f32, C.POINTER(SampleCtl), C.c_uint64, i64, i64, vp, vp, vp]),

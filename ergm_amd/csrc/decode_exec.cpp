@@ -12,7 +12,9 @@
 // (ergm_decode_bind_slots, serving ContinuousGenerator, where the step runs over all max_batch slots and ends with
 // the slot length update) the admission of new sequences into free slots (walk_admit: the prefill over packed ragged
 // rows) and the extension of occupied slots by more than one token (walk_extend: packed new rows over the slots' own
-// caches).  Those two share the blocks on engine 0 and the head tail (walk_packed).
+// caches).  Those two share the blocks on engine 0 (walk_blocks) and the head tail (walk_packed).  A fourth walk binds
+// nothing: ergm_decode_score (walk_score) runs the admission's packed rows through walk_blocks with the slot copies
+// left out and ends in ln_f over every row and ergm_lm_score.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +37,7 @@ int decode_slots_extend(const int* slot, const int* past, const int* n_new, cons
                         int max_len, int* lens, int* stop_lens, uint8_t* finished, hipStream_t s);
 int beam_select_launches();
 int beam_gather_launches(int n_layer);
+int lm_score_launches();
 
 // The row buffers a block runs on, for some number of rows R.
 struct Bufs {
@@ -184,6 +187,22 @@ size_t admit_carve(const ergm_decode_dims& d, int R, int Rc, int n_seq, AdmitWs*
     A->hl = c.take<float>(mb * E);
     A->lg = c.take<float>(mb * (size_t)d.vocab_pad);
     carve_gemm_ws(c, A->b, gemm_ws_need(d, R, Rc, n_seq));
+    return c.off;
+}
+
+// The buffers of one ergm_decode_score of R packed token rows and Rc packed caption rows: the block's rows, the caption
+// rows, ergm_lm_score's partials.  No head rows and no logits.
+size_t score_carve(const ergm_decode_dims& d, int R, int Rc, AdmitWs* A, void** lm_ws, size_t* lm_bytes, char* base) {
+    const size_t E = d.n_embd;
+    Carver c{base};
+    carve_rows(c, A->b, R, R, E, d.n_inner);
+    A->cap = c.take<__bf16>(Rc * E);
+    A->ckv = c.take<__bf16>(Rc * 2 * E);
+    A->hl = nullptr, A->lg = nullptr;
+    *lm_bytes = ergm_lm_score_workspace_size(R, d.vocab, d.n_embd);
+    *lm_ws = c.take<char>(*lm_bytes);
+    // the block GEMMs at exactly R and Rc rows; the head term of gemm_ws_need is one row's, which they cover
+    carve_gemm_ws(c, A->b, gemm_ws_need(d, R, Rc, 1));
     return c.off;
 }
 
@@ -354,8 +373,16 @@ struct MetaRows {
     const int *slot, *q0, *qn, *c0, *cn, *max_new, *last, *ones, *iota;
 };
 
-// The blocks and the head of an admission or an extension over the R packed rows the embedding left in ws.b.h, on
-// engine 0 (LayerNorm + ergm_gemm, as the Python path): a dry walk (w.dry) only counts.
+// The blocks over the R packed rows the embedding left in ws.b.h, on engine 0 (LayerNorm + ergm_gemm, as the Python
+// path): the loop the admission, the extension and the scoring walk share.  A dry walk (w.dry) only counts.
+template <class Self, class Before, class Cross>
+int walk_blocks(const ergm_decode_plan* P, Walk& w, const Packed& a, Self&& self_attn, Before&& before_cross, Cross&& cross_attn) {
+    for (int l = 0; l < P->d.n_layer; ++l) ERGM_TRY(block(P, w, a.ws.b, 0, a.R, l, self_attn, before_cross, cross_attn));
+    return ERGM_OK;
+}
+
+// The blocks and the head of an admission or an extension: the last row of every sequence -> ln_f -> the head ->
+// logits[slot].
 template <class Self, class Before, class Cross>
 int walk_packed(const ergm_decode_plan* P, Walk& w, const Packed& a, const MetaRows& m, Self&& self_attn, Before&& before_cross,
                 Cross&& cross_attn) {
@@ -363,8 +390,7 @@ int walk_packed(const ergm_decode_plan* P, Walk& w, const Packed& a, const MetaR
     const AdmitWs& W = a.ws;
     const int E = d.n_embd, n = a.n_seq;
     const int64_t h_row = (int64_t)E * 4, lg_row = (int64_t)d.vocab_pad * 4;  // bytes
-    for (int l = 0; l < d.n_layer; ++l) ERGM_TRY(block(P, w, W.b, 0, a.R, l, self_attn, before_cross, cross_attn));
-    // the last row of every sequence -> ln_f -> the head -> logits[slot]
+    ERGM_TRY(walk_blocks(P, w, a, self_attn, before_cross, cross_attn));
     if (w.on())
         ERGM_TRY(ergm_rows_to_slots(W.b.h, h_row, m.last, m.ones, m.iota, n, a.R, 1, W.hl, h_row, h_row, (int)h_row, n, 1, w.s));
     ERGM_TRY(ln(P, w, W.b, W.hl, n, P->p.ln_f_w, P->p.ln_f_b));
@@ -448,6 +474,52 @@ int walk_extend(const ergm_decode_plan* P, Walk& w, const Packed& x) {
         ERGM_TRY(decode_slots_extend(m.slot, past, m.qn, m.max_new, n, d.max_batch, d.max_len, P->lens, P->stop_lens, P->finished,
                                      w.s));
     return ERGM_OK;
+}
+
+// What ergm_decode_score adds to the packed call: the targets, the outputs and ergm_lm_score's workspace.
+struct ScoreOut {
+    const int64_t* targets;
+    float* logprob;
+    int* top1;
+    void* lm_ws;
+    size_t lm_bytes;
+};
+
+// The admission's walk with the slots left out: nothing bound is read or written.  The caption K | V of a layer stays
+// in ws.ckv, where the cross-attention reads it; the tail is ln_f over all R rows and ergm_lm_score.
+int walk_score(const ergm_decode_plan* P, Walk& w, const Packed& a, const ScoreOut& o) {
+    const ergm_decode_dims& d = P->d;
+    const int E = d.n_embd, H = d.n_head, R = a.R, Rc = a.Rc, n = a.n_seq;
+    const AdmitWs& W = a.ws;
+    const int *q0 = a.row(1), *qn = a.row(2), *c0 = a.row(3), *cn = a.row(4);
+    if (w.on())
+        ERGM_TRY(ergm_embed_packed(a.ids, a.tt, a.cap_ids, P->p.wte, P->p.wpe, a.vis, a.aud, a.has_feat, q0, qn, c0, cn, n, R, Rc,
+                                   a.max_n, a.max_c, W.b.h, W.cap, E, E, d.vocab_pad, d.n_positions, w.s));
+    auto self_attn = [&](int) -> int {
+        if (!w.on()) return ERGM_OK;
+        return ergm_attn_fwd_ragged(W.b.qkv, W.b.qkv + E, W.b.qkv + 2 * E, W.b.att, nullptr, q0, qn, q0, qn, n, H, R, R, a.max_n,
+                                    a.max_n, 3 * E, 3 * E, 3 * E, E, 1, w.s);
+    };
+    auto caption_kv = [&](int l) -> int {
+        return gemm(w, W.b, Rc, 2 * E, E, W.cap, reinterpret_cast<const __bf16*>(P->p.capkv_w_b) + (size_t)l * 2 * E, ERGM_KN,
+                    W.ckv, ERGM_BF16, ERGM_EPI_BIAS, P->p.capkv_b + (size_t)l * 2 * E, nullptr, nullptr, d.n_layer * 2 * E);
+    };
+    auto cross_attn = [&](int) -> int {
+        if (!w.on()) return ERGM_OK;
+        return ergm_attn_fwd_ragged(W.b.q, W.ckv, W.ckv + E, W.b.att, nullptr, q0, qn, c0, cn, n, H, R, Rc, a.max_n, a.max_c, E,
+                                    2 * E, 2 * E, E, 0, w.s);
+    };
+    ERGM_TRY(walk_blocks(P, w, a, self_attn, caption_kv, cross_attn));
+    ERGM_TRY(ln(P, w, W.b, W.b.h, R, P->p.ln_f_w, P->p.ln_f_b));
+    if (w.on(lm_score_launches()))
+        ERGM_TRY(ergm_lm_score(W.b.x, E, P->p.wte_b, E, o.targets, R, d.vocab, E, o.logprob, nullptr, nullptr, o.top1, o.lm_ws,
+                               o.lm_bytes, w.s));
+    return ERGM_OK;
+}
+
+bool score_rows_ok(const ergm_decode_dims& d, int max_rows, int max_cap_rows) {
+    return max_rows >= 1 && max_cap_rows >= 1 && (int64_t)max_rows <= (int64_t)d.max_batch * d.n_positions &&
+           (int64_t)max_cap_rows <= (int64_t)d.max_batch * d.cap_max && d.vocab <= 65536;
 }
 
 int slots_ready(const ergm_decode_plan* P, const char* what) {
@@ -738,6 +810,67 @@ extern "C" int ergm_decode_extend_launches(const ergm_decode_plan* P, int n_seq,
     admit_carve(P->d, rows, 1, n_seq, &x.ws, reinterpret_cast<char*>(P->b.h));
     Walk w{true, "decode_extend_launches"};
     ERGM_TRY(walk_extend(P, w, x));
+    return w.count;
+}
+
+extern "C" size_t ergm_decode_score_workspace_size(const ergm_decode_dims* dims, int max_rows, int max_cap_rows) {
+    if (!dims || !dims_ok(*dims) || !score_rows_ok(*dims, max_rows, max_cap_rows)) return 0;
+    AdmitWs A{};
+    void* lm = nullptr;
+    size_t lmb = 0;
+    // the block GEMMs' split-K workspace over every row count up to max_rows, as the admission sizes its own
+    const size_t rows = score_carve(*dims, max_rows, max_cap_rows, &A, &lm, &lmb, nullptr) - al256(A.b.gemm_ws_bytes);
+    return rows + al256(std::max<size_t>(16, gemm_ws_need(*dims, max_rows, max_cap_rows, 0)));
+}
+
+extern "C" int ergm_decode_score(ergm_decode_plan* P, int n_seq, const int* lens, const int* cap_lens, const int* meta,
+                                 const int64_t* ids, const int64_t* token_types, const int64_t* cap_ids, const float* vis,
+                                 const float* aud, const uint8_t* has_feat, const int64_t* targets, float* logprob, int* top1,
+                                 void* workspace, size_t ws_bytes, void* stream) {
+    ERGM_CHECK_ARG(P, "decode_score: null plan");
+    const ergm_decode_dims& d = P->d;
+    ERGM_CHECK_ARG(lens && cap_lens && meta && ids && cap_ids && targets && workspace, "decode_score: null argument");
+    ERGM_CHECK_ARG(n_seq >= 1 && n_seq <= d.max_batch, "decode_score: n_seq %d outside [1, max_batch %d]", n_seq, d.max_batch);
+    ERGM_CHECK_ARG((vis == nullptr) == (aud == nullptr), "decode_score: visual and audio features go together");
+    ERGM_CHECK_ARG(P->p.capkv_w_b && P->p.capkv_b, "decode_score: the plan was created without the caption K/V weights "
+                   "(capkv_w_b, capkv_b)");
+    ERGM_CHECK_ARG(d.vocab <= 65536, "decode_score: vocabulary %d > 65536 (ergm_lm_score)", d.vocab);
+    Packed a{};
+    int64_t R = 0, Rc = 0;
+    for (int b = 0; b < n_seq; ++b) {
+        ERGM_CHECK_ARG(lens[b] >= 2, "decode_score: sequence %d has %d tokens < 2 (nothing to score)", b, lens[b]);
+        ERGM_CHECK_ARG(lens[b] <= d.n_positions, "decode_score: sequence %d has %d tokens > n_positions %d", b, lens[b],
+                       d.n_positions);
+        ERGM_CHECK_ARG(cap_lens[b] >= 1 && cap_lens[b] <= d.cap_max, "decode_score: caption of sequence %d has %d rows outside "
+                       "[1, cap_max %d]", b, cap_lens[b], d.cap_max);
+        R += lens[b], Rc += cap_lens[b];
+        a.max_n = std::max(a.max_n, lens[b]), a.max_c = std::max(a.max_c, cap_lens[b]);
+    }
+    a.n_seq = n_seq, a.R = (int)R, a.Rc = (int)Rc;
+    ERGM_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "decode_score: workspace must be 256-byte aligned");
+    ERGM_CHECK_ARG(score_rows_ok(d, a.R, a.Rc), "decode_score: bad row counts");
+    ScoreOut o{targets, logprob, top1, nullptr, 0};
+    const size_t need = score_carve(d, a.R, a.Rc, &a.ws, &o.lm_ws, &o.lm_bytes, nullptr);  // this call alone
+    ERGM_CHECK_ARG(ws_bytes >= need, "decode_score: %d packed rows and %d caption rows need a workspace of %zu bytes, %zu given",
+                   a.R, a.Rc, need, ws_bytes);
+    score_carve(d, a.R, a.Rc, &a.ws, &o.lm_ws, &o.lm_bytes, reinterpret_cast<char*>(workspace));
+    a.meta = meta, a.ids = ids, a.tt = token_types, a.cap_ids = cap_ids;
+    a.vis = vis, a.aud = aud, a.has_feat = has_feat;
+    Walk w{false, "decode_score", as_stream(stream)};
+    return walk_score(P, w, a, o);
+}
+
+extern "C" int ergm_decode_score_launches(const ergm_decode_plan* P, int n_seq, int rows, int cap_rows) {
+    ERGM_CHECK_ARG(P && n_seq >= 1 && n_seq <= P->d.max_batch && rows >= 2 * (int64_t)n_seq && cap_rows >= n_seq &&
+                       score_rows_ok(P->d, rows, cap_rows),
+                   "decode_score_launches: bad plan or counts (n_seq %d rows %d cap_rows %d)", n_seq, rows, cap_rows);
+    Packed a{};
+    a.n_seq = n_seq, a.R = rows, a.Rc = cap_rows, a.max_n = rows, a.max_c = cap_rows;
+    ScoreOut o{};
+    // buffer addresses for the GEMM descriptors the walk plans (the plan's own workspace; nothing is launched)
+    score_carve(P->d, rows, cap_rows, &a.ws, &o.lm_ws, &o.lm_bytes, reinterpret_cast<char*>(P->b.h));
+    Walk w{true, "decode_score_launches"};
+    ERGM_TRY(walk_score(P, w, a, o));
     return w.count;
 }
 

@@ -849,6 +849,47 @@ def _u32_as_i32(x: int) -> int:
     return x - 2 ** 32 if x >= 2 ** 31 else x
 
 
+@dataclass
+class SequenceScore:
+    """What ``ContinuousGenerator.score`` returns for one sequence: ``logprobs[i]`` = log p(token first + i | the tokens
+    before it, captions, features) and ``top1[i]`` = the token the model ranks first at that position."""
+    logprobs: List[float]
+    top1: List[int]
+
+    @property
+    def sum(self) -> float:
+        return float(sum(self.logprobs))
+
+    @property
+    def ppl(self) -> float:
+        return math.exp(-self.sum / len(self.logprobs))
+
+
+def score_targets(ids: List[List[int]], first: List[int]) -> List[int]:
+    """The packed targets of a scoring group: packed row s of sequence b holds ids[b][s + 1] when s + 1 >= first[b], else
+    -100; a sequence's last row holds -100."""
+    out: List[int] = []
+    for seq, f in zip(ids, first):
+        out += [seq[s + 1] if s + 1 >= f else -100 for s in range(len(seq) - 1)] + [-100]
+    return out
+
+
+def score_groups(lens: List[int], max_admit: int, max_admit_tokens: int) -> List[tuple]:
+    """[lo, hi) index ranges that cut the sequences, in order, into groups of at most max_admit sequences and
+    max_admit_tokens packed rows: the scheduler's admission rule.  A sequence longer than max_admit_tokens fits none."""
+    groups, lo, rows = [], 0, 0
+    for i, n in enumerate(lens):
+        if n > max_admit_tokens:
+            raise ValueError(f"sequence {i} has {n} tokens > max_admit_tokens {max_admit_tokens}: it fits no group")
+        if i > lo and (i - lo >= max_admit or rows + n > max_admit_tokens):
+            groups.append((lo, i))
+            lo, rows = i, 0
+        rows += n
+    if len(lens) > lo:
+        groups.append((lo, len(lens)))
+    return groups
+
+
 class ContinuousGenerator:
     """In-flight batching over ``max_batch`` cache slots: requests are prefilled into free slots while the others keep
     decoding, every step runs over all slots, and a request's result does not depend on what it ran beside (bitwise
@@ -900,6 +941,7 @@ class ContinuousGenerator:
         self.row_steps = torch.zeros(mb, dtype=torch.int32, device=dev)
         self._ws = ops.attn_decode_workspace(mb, self.H, max(max_len, cap_max), dev)
         self._plan = self._plan_ws = self._plan_params = self._admit_ws = None
+        self._score_ws = self._plan_dims = None
         self._sampling = None   # (top_p, eos_id, sp2_id, seed) of the run in progress
         self.admit_calls = 0
         self.extend_calls = 0
@@ -933,7 +975,7 @@ class ContinuousGenerator:
 
     def _create_plan(self) -> None:
         self.m.refresh_bf16()
-        dims = self._new_plan(self.cap_max, capkv=True)
+        dims = self._plan_dims = self._new_plan(self.cap_max, capkv=True)
         plan = self._plan
         rows = min(self.sched.max_admit_tokens, self.max_batch * self.max_len)
         need_admit = L.load().ergm_decode_admit_workspace_size(C.byref(dims), rows, self.sched.max_admit * self.cap_max)
@@ -1040,8 +1082,12 @@ class ContinuousGenerator:
         if sps is not None:   # behind the admission: it set row_steps, which the minimum length counts from
             self._set_controls(slots, sps, torch.cat(ids_l).to(device=self.dev, dtype=torch.int64), q0, lens, reset=True)
 
-    def _admit_python(self, slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has) -> None:
-        E, H, dev, n_seq = self.E, self.H, self.dev, len(slots)
+    def _packed_python(self, ids_l, tt_l, cap_l, lens, clens, q0, c0, vis, aud, has, keep_kv=None, keep_ckv=None):
+        """The packed rows of n_seq sequences through the embedding and every block with the per-sequence kernels of the
+        static prefill: what the "python" admission and the "python" scoring share.  ``keep_kv(l, b, kv_rows)`` /
+        ``keep_ckv(l, b, ckv_rows)`` are called right behind sequence b's self-attention / before its cross-attention
+        with its K | V rows of layer l (the admission copies them to the slot).  Returns h [R, E] f32."""
+        E, H, dev, n_seq = self.E, self.H, self.dev, len(lens)
         R, Rc = sum(lens), sum(clens)
         wte, wpe = self._f("__wte_pad"), self._f("transformer.wpe.weight")
         h = torch.empty(R, E, dtype=torch.float32, device=dev)
@@ -1057,7 +1103,8 @@ class ContinuousGenerator:
             a = torch.empty(R, E, dtype=torch.bfloat16, device=dev)
             for b, r in enumerate(rows):
                 ops.attn_fwd(qkv[r, :E], qkv[r, E:2 * E], qkv[r, 2 * E:], 1, H, lens[b], lens[b], True, o=a[r])
-                self.kv[l][slots[b], :lens[b]].copy_(qkv[r, E:])
+                if keep_kv is not None:
+                    keep_kv(l, b, qkv[r, E:])
             return a
 
         def cross_attn(l, q):   # the captions' K | V of this layer, to the slots and under the queries
@@ -1065,12 +1112,25 @@ class ContinuousGenerator:
                              epilogue=L.EPI_BIAS)
             a = torch.empty(R, E, dtype=torch.bfloat16, device=dev)
             for b, (r, cr) in enumerate(zip(rows, crows)):
-                self.xkv[l][slots[b], :clens[b]].copy_(ckv[cr])
+                if keep_ckv is not None:
+                    keep_ckv(l, b, ckv[cr])
                 ops.attn_fwd(q[r], ckv[cr, :E], ckv[cr, E:], 1, H, lens[b], clens[b], False, o=a[r])
             return a
 
         for l in range(self.L):
             self._block(l, h, R, self_attn, cross_attn)
+        return h
+
+    def _admit_python(self, slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has) -> None:
+        dev, n_seq = self.dev, len(slots)
+
+        def keep_kv(l, b, kv_rows):
+            self.kv[l][slots[b], :lens[b]].copy_(kv_rows)
+
+        def keep_ckv(l, b, ckv_rows):
+            self.xkv[l][slots[b], :clens[b]].copy_(ckv_rows)
+
+        h = self._packed_python(ids_l, tt_l, cap_l, lens, clens, q0, c0, vis, aud, has, keep_kv, keep_ckv)
         last = torch.tensor([q0[b] + lens[b] - 1 for b in range(n_seq)], device=dev)
         sl = torch.tensor(slots, device=dev)
         self._logits[sl] = self._head(h.index_select(0, last))
@@ -1095,6 +1155,94 @@ class ContinuousGenerator:
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         L.call("ergm_decode_admit", self._plan, n_seq, arr(slots), arr(lens), arr(clens), arr(max_new), p(meta), p(ids), p(tt),
                p(cids), p(vis), p(aud), p(flags), p(self._admit_ws), self._admit_ws.numel(), self._stream())
+
+    # ---- scoring: what the model thinks of tokens it is handed ---------------------------------------------------
+    def score_launches(self, n_seq: int, rows: int, cap_rows: int) -> int:
+        """Kernel launches of one native scoring call of these sizes (ergm_decode_score_launches)."""
+        if self._plan is None:
+            raise ValueError("the python engine has no executor plan")
+        n = L.load().ergm_decode_score_launches(self._plan, n_seq, rows, cap_rows)
+        if n < 0:
+            L.check(n, "ergm_decode_score_launches")
+        return n
+
+    @torch.no_grad()
+    def score(self, sequences, first=None) -> List["SequenceScore"]:
+        """Teacher-forced scoring: for every sequence (a prompt tuple whose ``input_ids`` already hold the response) the
+        log-probability the model gives token s, s = first[b] .. n_b - 1, after the tokens before it, and the token it
+        would have preferred there.  ``first[b]`` in [1, n_b) defaults to 1.  The sequences are grouped in order under
+        ``max_admit`` / ``max_admit_tokens`` as the scheduler groups admissions; a group is one call and one read-back.
+        No slot, cache or length is touched: live and parked requests go on as if the call had not been made.
+        "native" / "fused": ergm_decode_score (no logits are written); "python": the per-sequence kernels of the
+        python admission, f32 logits for the group's rows, torch.log_softmax."""
+        self.m.refresh_bf16()
+        n_all = len(sequences)
+        first = [1] * n_all if first is None else [int(f) for f in first]
+        if len(first) != n_all:
+            raise ValueError("one first index per sequence")
+        lens = [int(p[0].numel()) for p in sequences]
+        clens = [int(p[2].numel()) for p in sequences]
+        for b, (n, c, f) in enumerate(zip(lens, clens, first)):
+            if c < 1:
+                raise ValueError(f"sequence {b} has an empty caption")
+            if n < 2 or n > self.cfg.n_positions or n > self.sched.max_admit_tokens or c > self.cap_max:
+                raise ValueError(f"sequence {b} ({n} tokens, {c} caption tokens) fits no scoring group (2 <= tokens <= "
+                                 f"min(n_positions {self.cfg.n_positions}, max_admit_tokens {self.sched.max_admit_tokens}), "
+                                 f"cap_max {self.cap_max})")
+            if not 1 <= f < n:
+                raise ValueError(f"first[{b}] = {f} outside [1, {n})")
+        out: List[SequenceScore] = []
+        for lo, hi in score_groups(lens, self.sched.max_admit, self.sched.max_admit_tokens):
+            grp, g_lens, g_first = sequences[lo:hi], lens[lo:hi], first[lo:hi]
+            targets = score_targets([p[0].reshape(-1).tolist() for p in grp], g_first)
+            run = self._score_python if self.engine == "python" else self._score_native
+            lp, t1 = run(grp, g_lens, clens[lo:hi], torch.tensor(targets, dtype=torch.int64).to(self.dev))
+            lp, t1 = lp.tolist(), t1.tolist()
+            q = 0
+            for n, f in zip(g_lens, g_first):
+                out.append(SequenceScore(lp[q + f - 1:q + n - 1], t1[q + f - 1:q + n - 1]))
+                q += n
+        return out
+
+    def _score_python(self, grp, lens, clens, targets):
+        """(logprob, top1) of the group's R packed rows on the CPU, unscored rows 0: the yardstick."""
+        n_seq, V = len(grp), self.m.layout.vocab
+        q0 = [sum(lens[:b]) for b in range(n_seq)]
+        c0 = [sum(clens[:b]) for b in range(n_seq)]
+        vis, aud, has = self._features(grp)
+        h = self._packed_python([p[0].reshape(-1) for p in grp], [p[1].reshape(-1) for p in grp],
+                                [p[2].reshape(-1) for p in grp], lens, clens, q0, c0, vis, aud, has)
+        logits = self._head(h)[:, :V]
+        lsm = torch.log_softmax(logits, dim=-1)
+        valid = (targets >= 0) & (targets < V)
+        lp = lsm.gather(1, targets.clamp(0, V - 1)[:, None])[:, 0]
+        lp = torch.where(valid, lp, torch.zeros_like(lp))
+        return lp.cpu(), logits.argmax(-1).cpu()
+
+    def _score_native(self, grp, lens, clens, targets):
+        dev, n_seq, R = self.dev, len(grp), sum(lens)
+        if self._score_ws is None:
+            rows = min(self.sched.max_admit_tokens, self.max_batch * self.cfg.n_positions)
+            need = L.load().ergm_decode_score_workspace_size(C.byref(self._plan_dims), rows, self.sched.max_admit * self.cap_max)
+            if need == 0:
+                raise ValueError("the decode executor cannot score with this model's dimensions")
+            self._score_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        q0 = [sum(lens[:b]) for b in range(n_seq)]
+        c0 = [sum(clens[:b]) for b in range(n_seq)]
+        zero = [0] * n_seq
+        meta = torch.tensor([zero, q0, lens, c0, clens, zero, zero, [a + n - 1 for a, n in zip(q0, lens)], [1] * n_seq,
+                             list(range(n_seq))], dtype=torch.int32).to(dev)
+        cat = lambda i: torch.cat([p[i].reshape(-1) for p in grp]).to(device=dev, dtype=torch.int64)
+        ids, tt, cids = cat(0), cat(1), cat(2)
+        vis, aud, has = self._features(grp)
+        flags = None if vis is None else torch.tensor(has, dtype=torch.uint8).to(dev)
+        out = torch.empty(2, R, dtype=torch.int32, device=dev)   # logprob (f32 bits) | top1: one read-back
+        arr = lambda v: (C.c_int * n_seq)(*v)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        L.call("ergm_decode_score", self._plan, n_seq, arr(lens), arr(clens), p(meta), p(ids), p(tt), p(cids), p(vis), p(aud),
+               p(flags), p(targets), p(out[0]), p(out[1]), p(self._score_ws), self._score_ws.numel(), self._stream())
+        host = out.cpu()
+        return host[0].view(torch.float32), host[1]
 
     # ---- extension: more than one token behind a cache that holds a past -------------------------------------
     @torch.no_grad()

@@ -89,6 +89,32 @@ def linear_rows(A: torch.Tensor, W: torch.Tensor, M: int, N: int, K: int, w_layo
     return out
 
 
+def lm_score(x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, V: int, R: Optional[int] = None,
+             want=("logprob", "lse", "top1_logit", "top1"), ws: Optional[torch.Tensor] = None):
+    """The tied head and the log-softmax of every row without the logits (ergm_lm_score): x bf16 [>= R, K], w bf16
+    [>= V, K], targets int64 [R] (outside [0, V): the row is not scored and its logprob is exactly 0).  Returns the
+    tuple ``(logprob, lse, top1_logit, top1)`` (f32, f32, f32, int32, [R] each) with None for a name not in ``want``.
+    ``ws``: a uint8 workspace to reuse."""
+    _need_gpu(x, w, targets)
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or targets.dtype != torch.int64:
+        raise ValueError("lm_score: x and w are bf16, targets int64")
+    if x.dim() != 2 or w.dim() != 2 or x.stride(1) != 1 or w.stride(1) != 1 or not targets.is_contiguous():
+        raise ValueError("lm_score: x and w are 2-d with unit column stride, targets contiguous")
+    R = x.shape[0] if R is None else R
+    K = x.shape[1]
+    if w.shape[1] != K or w.shape[0] < V or x.shape[0] < R or targets.numel() < R:
+        raise ValueError("lm_score: w is [>= V, K], x [>= R, K], targets [>= R]")
+    dev = x.device
+    out = [torch.empty(R, dtype=torch.int32 if n == "top1" else torch.float32, device=dev) if n in want else None
+           for n in ("logprob", "lse", "top1_logit", "top1")]
+    need = L.load().ergm_lm_score_workspace_size(R, V, K)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    L.call("ergm_lm_score", _ptr(x), x.stride(0), _ptr(w), w.stride(0), _ptr(targets), R, V, K, *[_ptr(o) for o in out],
+           _ptr(ws), ws.numel(), _stream(dev))
+    return tuple(out)
+
+
 def gemm_f8(A8: torch.Tensor, a_scale: torch.Tensor, B8t: torch.Tensor, b_scale: torch.Tensor,
             out: Optional[torch.Tensor] = None, out_dtype=torch.float32, epilogue: int = L.EPI_NONE,
             bias: Optional[torch.Tensor] = None, aux: Optional[torch.Tensor] = None,

@@ -155,6 +155,48 @@ class Trainer:
         hyps = gen.generate(prompts, top_p, eos_id, sp2_id, seed, sampling=sampling)
         return hyps, refs, emos, [float(x) for x in torch.stack(losses).tolist()]
 
+    @torch.no_grad()
+    def score(self, loader, max_batch: int = 8, engine: str = "python"):
+        """Per-sample log-likelihood of the reference responses: for every sample of ``loader`` the sequence up to its
+        last position with ``labels != -100`` goes through ``ContinuousGenerator.score``, and the positions summed are
+        exactly those the training loss scores, with its shift (position s counts when labels[s] != -100, s >= 1, and
+        the token scored there is labels[s]: the input token, except at the sequence's last position, where the collate
+        puts eos and the label takes the input's place, which no scored row reads).  Returns ``(per_sample, ppl)``:
+        per_sample[i] = (Σ logprob, count) in loader order, ppl = exp(-Σ / Σ count) over all of them.  No logits
+        matrix is written on the "native" / "fused" engines."""
+        from .generate import ContinuousGenerator
+        self.model.eval()
+        seqs, picks, where = [], [], []
+        per_sample = []
+        for batch in DevicePrefetcher(loader, self.device):
+            ids, tts, labels, caps = batch["input_ids"], batch["token_type_ids"], batch["labels"], batch["caption_ids"]
+            imgs, auds = batch.get("visual_feat"), batch.get("audio_feat")
+            lab, idl = labels.tolist(), ids.tolist()
+            for i, row in enumerate(lab):
+                pos = [s for s in range(1, len(row)) if row[s] != -100]
+                if any(row[s] != idl[i][s] for s in pos[:-1]):
+                    raise ValueError("score: a label differs from the input token a later position reads")
+                per_sample.append((0.0, 0))
+                if not pos:
+                    continue
+                n = pos[-1] + 1
+                seq = ids[i, :n].clone()
+                seq[n - 1] = labels[i, n - 1]
+                seqs.append((seq, tts[i, :n], caps[i], None if imgs is None else imgs[i],
+                             None if auds is None else auds[i]))
+                picks.append([s - pos[0] for s in pos])
+                where.append((len(per_sample) - 1, pos[0]))
+        if seqs:
+            cfg = self.model.config
+            gen = ContinuousGenerator(self.model, max_batch=max_batch, max_len=cfg.n_positions,
+                                      cap_max=max(int(p[2].numel()) for p in seqs), engine=engine)
+            scores = gen.score(seqs, first=[f for _, f in where])
+            for (i, _), pick, sc in zip(where, picks, scores):
+                per_sample[i] = (float(sum(sc.logprobs[j] for j in pick)), len(pick))
+        total, count = sum(p[0] for p in per_sample), sum(p[1] for p in per_sample)
+        ppl = math.exp(-total / count) if count else float("nan")
+        return per_sample, ppl
+
     def train(self, train_loader, valid_loader, num_epochs: int, log=print,
               seed: Optional[int] = None) -> Tuple[EpochStats, EpochStats]:
         """src/main.py:125-204: epochs of training + validation, keeping the best-PPL checkpoint.  ``seed``: as the

@@ -916,6 +916,56 @@ int ergm_beam_gather(void* const* caches, int n_layer, int64_t ld_seq, int64_t l
 int ergm_decode_run_beams(ergm_decode_plan* plan, int n, int W, int64_t eos_id, int64_t sp2_id, float* scores,
                           int64_t* tokens_out, int* parents_out, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- Scoring given tokens (found by symbol, ABI unchanged) ---------------------------------------------------------
+ * ergm_lm_score: the tied LM head and the log-softmax of R rows in one pass; no logits are written.  For row r and the
+ * columns j < V, x_j = Σ_k X[r][k]·W[j][k] (bf16 operands, f32 accumulation, never rounded to bf16), and
+ *     lse[r]        = m + logf(Σ_j expf(x_j - m)), m the row's largest logit,
+ *     top1[r]       = the column of the largest x_j, ties to the lowest column; top1_logit[r] = its value,
+ *     logprob[r]    = x_target - lse, or exactly 0.0f when targets[r] lies outside [0, V) (the row is not scored; its
+ *                     lse and top1 are still written).
+ * X: bf16 [R][ldx], the ln_f rows; W: bf16 [>= V rows][ldw] (ERGM_NK), the tied head.  Rows of W at or past V (the pad
+ * of vocab_pad) never contribute whatever they hold, NaN included, and rows of X at or past R are never read.  Any of
+ * the four outputs may be NULL.  The vocabulary is cut into partitions of 512 columns, a function of V alone; a
+ * workgroup runs an online softmax over one partition for 64 rows and leaves one (max, Σexp, argmax) per row, and a
+ * second launch folds the partitions in ascending order.  No atomics: the same bits in every run, and a row's outputs
+ * are bitwise the same whatever other rows the call holds and wherever the row sits.
+ * workspace: 16-byte aligned, at least ergm_lm_score_workspace_size(R, V, K) = (3·ceil(V / 512) + 1)·R·4 bytes (0 for
+ * dimensions the call rejects).  ERGM_EINVAL before any launch unless R >= 1, 1 <= V <= 65,536, K a positive multiple
+ * of 64, ldx and ldw >= K and multiples of 8, X and W 16-byte aligned, and for a NULL X / W / targets or a short
+ * workspace.                                                                                                        */
+size_t ergm_lm_score_workspace_size(int R, int V, int K);
+int ergm_lm_score(const void* X, int ldx, const void* W, int ldw, const int64_t* targets, int R, int V, int K,
+                  float* logprob, float* lse, float* top1_logit, int* top1, void* workspace, size_t ws_bytes,
+                  void* stream);
+
+/* ergm_decode_score: teacher-forced scoring of n_seq given sequences, the admission's walk with the slots left out:
+ * ergm_embed_packed; per layer ergm_layernorm_fwd / ergm_gemm (split_k = 0) over the R = Σ n_b packed rows, ragged causal
+ * attention (ergm_attn_fwd_ragged alone: no K | V row goes to a slot), the caption K | V GEMM over the Rc = Σ c_b packed
+ * caption rows, read in place by the ragged cross-attention, the MLP; then ln_f over all R rows and ergm_lm_score against
+ * `targets` with V = vocab.  Engine 0's kernels whatever engine the plan is set to.  It reads and writes no cache, no
+ * lens, no finished flag and no logits: the plan needs no bind, and with slots bound it may be called between steps
+ * while requests are live or parked.  12 launches per block + 4 when no GEMM splits, whatever n_seq is.
+ *   lens (= n_b), cap_lens: HOST int [n_seq], checked here; ERGM_EINVAL before any launch for n_seq outside
+ *     [1, max_batch], n_b < 2 (no position to score), n_b > n_positions, c_b outside [1, cap_max], a vocabulary above
+ *     65,536, a NULL lens / cap_lens / meta / ids / cap_ids / targets / workspace, or more packed rows than the workspace
+ *     holds.
+ *   meta: DEVICE int [ERGM_ADMIT_META_ROWS][n_seq] in ergm_decode_admit's layout; rows 0, 5 and 6 are ignored.
+ *   ids, token_types (may be NULL), cap_ids, vis / aud, has_feat: as ergm_decode_admit takes them.
+ *   targets: device int64 [R], the token each packed row is scored against, or a value outside [0, vocab) for a row that
+ *     is not scored (the caller shifts: row s of a sequence holds its token s + 1, the last row none).
+ *   logprob: device f32 [R], log p(target | the row's prefix), exactly 0 for a row not scored; top1: device int32 [R], the
+ *     model's most probable token at every row.  Either may be NULL.
+ *   workspace: 256-byte aligned, at least ergm_decode_score_workspace_size(dims, max_rows, max_cap_rows) bytes for any call
+ *     of at most that many rows (0 for dimensions or row counts it rejects: max_rows <= max_batch · n_positions,
+ *     max_cap_rows <= max_batch · cap_max); linear in the rows, nothing of size R x vocab.
+ * ergm_decode_score_launches: the kernel launches of one such call, counted by walking its launch sequence dry; host only. */
+size_t ergm_decode_score_workspace_size(const ergm_decode_dims* dims, int max_rows, int max_cap_rows);
+int ergm_decode_score(ergm_decode_plan* plan, int n_seq, const int* lens, const int* cap_lens, const int* meta,
+                      const int64_t* ids, const int64_t* token_types, const int64_t* cap_ids, const float* vis,
+                      const float* aud, const uint8_t* has_feat, const int64_t* targets, float* logprob, int* top1,
+                      void* workspace, size_t ws_bytes, void* stream);
+int ergm_decode_score_launches(const ergm_decode_plan* plan, int n_seq, int rows, int cap_rows);
+
 /* Library information and errors. */
 int ergm_version(void);
 int ergm_last_error(char* buf, size_t n);
