@@ -89,6 +89,13 @@ class SampleCtl(C.Structure):
                 ("min_step", C.c_void_p), ("seen", C.c_void_p), ("ld_seen", C.c_int)]
 
 
+class LogitRules(C.Structure):
+    """ergm_logit_rules (ergm_hip.h): the token histories and the per-row rule values, None for a rule that is off."""
+    _fields_ = [("hist", C.c_void_p), ("ld_hist", C.c_int), ("start", C.c_void_p), ("ngram", C.c_void_p),
+                ("bad", C.c_void_p), ("ld_bad", C.c_int)]
+
+
+NGRAM_MAX = 8  # ERGM_NGRAM_MAX
 vp, i32, i64, f32, f64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 _SIGS = {
     "ergm_version": (i32, []),
@@ -152,6 +159,11 @@ _SIGS = {
     "ergm_beam_select": (i32, [vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
     "ergm_beam_gather": (i32, [C.POINTER(vp), i32, i64, i64, i32, vp, vp, i32, i32, i32, vp]),
     "ergm_decode_run_beams": (i32, [vp, i32, i32, i64, i64, vp, vp, vp, vp, sz, vp]),
+    "ergm_logit_rules_apply": (i32, [vp, i32, i32, i32, C.POINTER(LogitRules), vp, vp, i64, i32, vp]),
+    "ergm_hist_write": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, vp, i32, i32, vp]),
+    "ergm_hist_append": (i32, [vp, vp, vp, i32, vp, i32, i32, vp]),
+    "ergm_hist_follow": (i32, [vp, i32, vp, vp, i32, i32, i32, vp]),
+    "ergm_decode_set_rules": (i32, [vp, C.POINTER(LogitRules)]),
     "ergm_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "ergm_layernorm_bwd_workspace_size": (sz, [i32, i32]),
     "ergm_layernorm_bwd": (i32, [vp] * 10 + [sz, i32, i32, vp, vp]),

@@ -79,6 +79,9 @@ struct ergm_decode_plan {
     int* stop_lens;
     uint32_t* row_ids;
     uint32_t* row_steps;
+    // logit rules (ergm_decode_set_rules): applied by the sampled slot loop and the beam loop while set
+    bool ruled;
+    ergm_logit_rules rules;
 };
 
 namespace {
@@ -635,6 +638,21 @@ extern "C" int ergm_decode_set_engine(ergm_decode_plan* P, int engine) {
     return ERGM_OK;
 }
 
+extern "C" int ergm_decode_set_rules(ergm_decode_plan* P, const ergm_logit_rules* rules) {
+    ERGM_CHECK_ARG(P, "decode_set_rules: null plan");
+    if (!rules) {
+        P->ruled = false;
+        P->rules = ergm_logit_rules{};
+        return ERGM_OK;
+    }
+    ERGM_CHECK_ARG(rules->hist && rules->ld_hist >= P->d.max_len && P->d.max_len <= 1024,
+                   "decode_set_rules: null hist, ld_hist %d < max_len %d, or max_len above 1024", rules->ld_hist, P->d.max_len);
+    ERGM_CHECK_ARG(!rules->bad || rules->ld_bad >= 1, "decode_set_rules: ld_bad %d < 1", rules->ld_bad);
+    P->rules = *rules;
+    P->ruled = rules->ngram || rules->bad;
+    return ERGM_OK;
+}
+
 extern "C" int ergm_decode_step(ergm_decode_plan* P, const int64_t* tokens, const int64_t* token_types, void* stream) {
     ERGM_TRY(step_ready(P, 1, "decode_step"));
     ERGM_CHECK_ARG(tokens, "decode_step: null tokens");
@@ -691,6 +709,8 @@ extern "C" int ergm_decode_run_beams(ergm_decode_plan* P, int n, int W, int64_t 
         int64_t* tok = tokens_out + (size_t)i * B;
         int* par = parents_out + (size_t)i * B;
         Walk w{false, "decode_run_beams", s};
+        if (P->ruled)
+            ERGM_TRY(ergm_logit_rules_apply(P->logits, d.vocab_pad, B, d.vocab, &P->rules, P->lens, P->finished, eos_id, d.max_len, s));
         if (w.on(beam_select_launches()))
             ERGM_TRY(ergm_beam_select(P->logits, d.vocab_pad, B, W, d.vocab, scores, P->finished, eos_id, par, tok, workspace,
                                       ws_bytes, s));
@@ -698,6 +718,10 @@ extern "C" int ergm_decode_run_beams(ergm_decode_plan* P, int n, int W, int64_t 
         if (w.on(beam_gather_launches(d.n_layer)))
             ERGM_TRY(ergm_beam_gather(P->kv.data(), d.n_layer, (int64_t)d.max_len * kv_row, kv_row, (int)kv_row, par, P->lens, B, W,
                                       P->n_max, s));
+        if (P->ruled) {  // the histories follow the caches, then take the round's tokens
+            ERGM_TRY(ergm_hist_follow(P->rules.hist, P->rules.ld_hist, par, P->lens, B, W, d.max_len, s));
+            ERGM_TRY(ergm_hist_append(tok, P->lens, P->finished, B, P->rules.hist, P->rules.ld_hist, d.max_len, s));
+        }
         ERGM_TRY(walk(P, w, P->engine, B, tok, P->tt));
         P->n_max += 1;
     }
@@ -895,12 +919,16 @@ static int run_slots(ergm_decode_plan* P, const char* what, int n, float top_p, 
     ERGM_TRY(decode_fill_i64(P->tt, sp2_id, B, s));
     for (int i = 0; i < n; ++i) {
         int64_t* tok = tokens_out + (size_t)i * B;
+        const bool ruled = ctl && P->ruled;
+        if (ruled)
+            ERGM_TRY(ergm_logit_rules_apply(P->logits, d.vocab_pad, B, d.vocab, &P->rules, P->lens, P->finished, eos_id, d.max_len, s));
         if (ctl)
             ERGM_TRY(ergm_sample_rows(P->logits, d.vocab_pad, B, d.vocab, top_p, ctl, seed, P->row_ids, P->row_steps, P->finished,
                                       eos_id, tok, nullptr, nullptr, logprobs_out ? logprobs_out + (size_t)i * B : nullptr, s));
         else
             ERGM_TRY(ergm_topp_sample_rows(P->logits, d.vocab_pad, B, d.vocab, top_p, seed, P->row_ids, P->row_steps, P->finished,
                                            eos_id, tok, nullptr, nullptr, s));
+        if (ruled) ERGM_TRY(ergm_hist_append(tok, P->lens, P->finished, B, P->rules.hist, P->rules.ld_hist, d.max_len, s));
         Walk w{false, "decode_step", s};
         ERGM_TRY(walk(P, w, P->engine, B, tok, P->tt));
     }

@@ -489,15 +489,42 @@ class BatchedGenerator:
             raise ValueError(f"{n_prompts} prompts of {num_beams} beams for max_batch {self.max_batch}")
 
     @torch.no_grad()
-    def beam_prefill(self, prompts, num_beams: int, eos_id: Optional[int] = None, sp2_id: Optional[int] = None):
+    def beam_prefill(self, prompts, num_beams: int, eos_id: Optional[int] = None, sp2_id: Optional[int] = None,
+                     no_repeat_ngram_size: int = 0, no_repeat_scope: str = "sequence", bad_words_ids=()):
         """The state round 0 of a beam search starts from (ergm_hip.h, ergm_decode_run_beams): prompt g in row
         g·num_beams alone (cache rows, length, logits), its caption K | V in all rows of its group, ``beam_scores``
         [0, -inf, ...] per group, nothing finished.  ``eos_id`` / ``sp2_id`` are kept for ``beam_round``.  Returns the
-        prompts' next-token logits [G, V]."""
+        prompts' next-token logits [G, V].
+
+        ``no_repeat_ngram_size`` / ``no_repeat_scope`` / ``bad_words_ids`` (``SamplingParams`` has their meaning; one
+        setting for all prompts) make every round ban before it selects (ergm_hip.h, "Logit rules"): the prompt goes
+        into the token history of row g·num_beams here, round 0's fan-out copies it to the group's other rows, and
+        "turn" counts the generated part only.  A candidate's log-probability is then normalised over the tokens its
+        beam may still take, where Hugging Face masks after the log-softmax."""
         self._beam_check(len(prompts), num_beams)
+        bad = check_rules(no_repeat_ngram_size, no_repeat_scope, bad_words_ids)
+        ruled = no_repeat_ngram_size > 0 or bool(bad)
+        if ruled and self.max_len > 1024:
+            raise ValueError(f"logit rules need max_len <= 1024 (it is {self.max_len})")
         W = num_beams
         self._prefill(prompts, W)
         R = self.B
+        self._beam_rules = None
+        if ruled:   # one copy to the device: the prompts' rows of the history, start | ngram | the pool row per row
+            pool = pack_bad_words(bad, sum(len(w) + 1 for w in bad) + 1)
+            rows = []
+            for p in prompts:
+                ids = [int(t) for t in p[0].reshape(-1).tolist()]
+                vals = [len(ids) if no_repeat_scope == "turn" else 0, no_repeat_ngram_size, *pool]
+                rows.append(vals + ids + [0] * (self.max_len - len(ids)))
+                rows += [vals + [0] * self.max_len] * (W - 1)
+            m = torch.tensor(rows, dtype=torch.int32).to(self.dev)
+            k = 2 + len(pool)
+            self._beam_hist = m[:, k:].contiguous()
+            self._beam_rule_vals = (m[:, 0].contiguous(), m[:, 1].contiguous(), m[:, 2:k].contiguous())
+            self._beam_rules = ops.rules_desc(self._beam_hist, *self._beam_rule_vals)
+        if self.engine != "python":
+            L.call("ergm_decode_set_rules", self._plan, None if self._beam_rules is None else C.byref(self._beam_rules))
         self.beam_W, self._beam_ids = W, (eos_id, sp2_id)
         self.beam_scores = torch.full((R,), -math.inf, dtype=torch.float32, device=self.dev)
         self.beam_scores[::W] = 0.0
@@ -526,6 +553,7 @@ class BatchedGenerator:
         toks = torch.empty(n, R, dtype=torch.int64, device=dev)
         pars = torch.empty(n, R, dtype=torch.int32, device=dev)
         fin = self.finished[:R]
+        rules = getattr(self, "_beam_rules", None)
         if self.engine != "python":
             p = lambda t: C.c_void_p(t.data_ptr())
             L.call("ergm_decode_run_beams", self._plan, n, W, eos_id, sp2_id, p(self.beam_scores), p(toks), p(pars),
@@ -535,9 +563,14 @@ class BatchedGenerator:
             tt = torch.full((R,), sp2_id, dtype=torch.int64, device=dev)
             lens = self.lens[:R]
             for i in range(n):
+                if rules is not None:
+                    ops.logit_rules(self._logits, V, rules, self.lens, eos_id, self.max_len, finished=fin)
                 ops.beam_select(self._logits, V, W, self.beam_scores, fin, eos_id, parent=pars[i], token=toks[i],
                                 ws=self._beam_ws)
                 ops.beam_gather(self.kv, pars[i], self.lens, W, max_len=self.n_max)
+                if rules is not None:
+                    ops.hist_follow(self._beam_hist, pars[i], self.lens, W, self.max_len)
+                    ops.hist_append(toks[i], self.lens, self._beam_hist, self.max_len, finished=fin)
                 self._logits = self._step_rows(toks[i], tt, lens, self.cap_lens[:R], [t[:R] for t in self.kv], self.xkv)
                 lens.add_((fin == 0).to(torch.int32))
                 self.n_max += 1
@@ -545,13 +578,15 @@ class BatchedGenerator:
 
     @torch.no_grad()
     def beam_search(self, prompts, num_beams: int, eos_id: int, sp2_id: int, max_new_tokens: Optional[int] = None,
-                    length_penalty: float = 1.0, num_return: int = 1):
+                    length_penalty: float = 1.0, num_return: int = 1, no_repeat_ngram_size: int = 0,
+                    no_repeat_scope: str = "sequence", bad_words_ids=()):
         """Beam search of ``num_beams`` beams per prompt, the responses typed as speaker 2: the prefill, then chunks of
         8 rounds with a look at ``finished`` in between, until every row is finished or ``max_new_tokens`` rounds ran.
         Returns, per prompt, ``num_return`` pairs ``(tokens, sum_logprob)``, best first by
         ``sum_logprob / len(tokens) ** length_penalty`` (ties by row); each hypothesis ends at its first ``eos_id``
         (included) or at ``max_new_tokens``.  The device ranks the beams by the raw sum of log-probabilities: the
-        length penalty acts on this final ordering only, not during the search."""
+        length penalty acts on this final ordering only, not during the search.  ``no_repeat_ngram_size`` /
+        ``no_repeat_scope`` / ``bad_words_ids``: ``beam_prefill``'s, one setting for all prompts."""
         self._beam_check(len(prompts), num_beams)
         if isinstance(num_return, bool) or not isinstance(num_return, int) or not 1 <= num_return <= num_beams:
             raise ValueError(f"num_return {num_return!r} outside [1, num_beams {num_beams}]")
@@ -562,7 +597,7 @@ class BatchedGenerator:
             max_new_tokens = bound
         if max_new_tokens < 1 or max_new_tokens > bound:
             raise ValueError(f"max_new_tokens {max_new_tokens} outside [1, {bound}] (max_len - the longest prompt)")
-        self.beam_prefill(prompts, num_beams, eos_id, sp2_id)
+        self.beam_prefill(prompts, num_beams, eos_id, sp2_id, no_repeat_ngram_size, no_repeat_scope, bad_words_ids)
         tokens, parents, done = [], [], 0
         while True:
             n = min(8, max_new_tokens - done)
@@ -605,6 +640,44 @@ def beam_backtrack(tokens, parents, scores, num_beams: int, eos_id: int, length_
 
 
 NO_REQUEST = -1
+NGRAM_MAX = L.NGRAM_MAX          # the longest n-gram and the longest bad-word sequence (ERGM_NGRAM_MAX)
+RULE_SCOPES = ("sequence", "turn")
+
+
+def check_rules(no_repeat_ngram_size, no_repeat_scope, bad_words_ids) -> tuple:
+    """Validate the arguments of the logit rules (ergm_hip.h, "Logit rules") and return ``bad_words_ids`` as a tuple of
+    tuples: n an integer in [0, 8], the scope "sequence" or "turn", every sequence of 1 .. 8 ids >= 0."""
+    n = no_repeat_ngram_size
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= NGRAM_MAX:
+        raise ValueError(f"no_repeat_ngram_size {n!r} is not an integer in [0, {NGRAM_MAX}]")
+    if no_repeat_scope not in RULE_SCOPES:
+        raise ValueError(f"no_repeat_scope {no_repeat_scope!r} is not one of {RULE_SCOPES}")
+    if isinstance(bad_words_ids, (str, bytes)) or not hasattr(bad_words_ids, "__iter__"):
+        raise ValueError("bad_words_ids must be a sequence of token-id sequences")
+    words = []
+    for w in bad_words_ids:
+        if isinstance(w, (str, bytes)) or not hasattr(w, "__iter__"):
+            raise ValueError("bad_words_ids must be a sequence of token-id sequences")
+        w = tuple(w)
+        if not 1 <= len(w) <= NGRAM_MAX:
+            raise ValueError(f"a bad-word sequence has {len(w)} tokens: outside [1, {NGRAM_MAX}]")
+        for t in w:
+            if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 31:
+                raise ValueError(f"bad-word token {t!r} is not an integer in [0, 2^31)")
+        words.append(w)
+    return tuple(words)
+
+
+def pack_bad_words(bad_words_ids, cap: int) -> List[int]:
+    """The pool row of a bad-word list: each sequence as its length followed by its tokens, zeros to ``cap`` (a zero
+    length ends the run; a list that fills the row exactly needs none).  ValueError when it does not fit."""
+    row: List[int] = []
+    for w in bad_words_ids:
+        row += [len(w), *w]
+    if len(row) > cap:
+        raise ValueError(f"bad_words_ids take {len(row)} pool entries (one per token and one per sequence) > "
+                         f"bad_words_cap {cap}")
+    return row + [0] * (cap - len(row))
 
 
 @dataclass(frozen=True)
@@ -612,15 +685,26 @@ class SamplingParams:
     """What one request asks of the sampler (ergm_sample_rows applies them in this order): ``repetition_penalty`` over
     the tokens its cache holds and the ones it drew, no eos before ``min_new_tokens`` tokens of the turn,
     ``temperature``, ``top_k`` (0: off; 1: greedy), then ``top_p`` over what top-k left (None: the run's).
-    ``logprobs``: keep the log-probability of every returned token (``ContinuousGenerator.token_logprobs``)."""
+    ``logprobs``: keep the log-probability of every returned token (``ContinuousGenerator.token_logprobs``).
+
+    Two bans precede all of these (ergm_logit_rules_apply; a banned token holds no mass, eos is never banned):
+    ``no_repeat_ngram_size`` = n in 1 .. 8: no n-gram may occur twice, Hugging Face's NoRepeatNGramLogitsProcessor, over
+    the whole sequence, prompt included (``no_repeat_scope="sequence"``), or over the tokens generated in the current
+    turn only (``"turn"``: the other speaker's words and earlier turns do not count); ``bad_words_ids``: sequences of
+    1 .. 8 token ids none of which may be completed (lists are accepted and stored as tuples)."""
     top_p: Optional[float] = None
     temperature: float = 1.0
     top_k: int = 0
     repetition_penalty: float = 1.0
     min_new_tokens: int = 0
     logprobs: bool = False
+    no_repeat_ngram_size: int = 0
+    no_repeat_scope: str = "sequence"
+    bad_words_ids: tuple = ()
 
     def __post_init__(self):
+        object.__setattr__(self, "bad_words_ids",
+                           check_rules(self.no_repeat_ngram_size, self.no_repeat_scope, self.bad_words_ids))
         for name in ("top_p", "temperature", "repetition_penalty"):
             v = getattr(self, name)
             if v is None and name == "top_p":
@@ -633,6 +717,10 @@ class SamplingParams:
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 31:
                 raise ValueError(f"{name} {v!r} is not an integer in [0, 2^31)")
+
+    @property
+    def has_rules(self) -> bool:
+        return self.no_repeat_ngram_size > 0 or bool(self.bad_words_ids)
 
     def check_bound(self, max_new_tokens: int) -> None:
         if self.min_new_tokens > max_new_tokens:
@@ -660,7 +748,9 @@ class SlotScheduler:
       tokens as n lists of one token per slot, finished as one flag per slot, read back once;
     * ``backend.retire(slot, request)`` (optional) is told when a request leaves its slot or is parked in it;
     * ``backend.extend_requests(slots, requests)`` (optional; needed by ``extend``) appends the ``.n`` new tokens of
-      each continuation (``.payload``) behind the ``.past`` rows its slot holds.
+      each continuation (``.payload``) behind the ``.past`` rows its slot holds;
+    * ``backend.check_sampling(sampling)`` (optional) raises ValueError at ``submit`` / ``extend`` for a
+      ``SamplingParams`` the backend cannot serve, so that a refused request leaves nothing behind.
 
     Requests wait in arrival order (FIFO) and are admitted at a look, at most ``max_admit`` sequences and
     ``max_admit_tokens`` packed prompt rows per ``admit`` call, as many calls as fill the free slots; a request that does
@@ -721,6 +811,7 @@ class SlotScheduler:
             raise ValueError(f"max_new_tokens {max_new_tokens} outside [1, {self.max_len - n}] (max_len - the prompt)")
         if sampling is not None:
             sampling.check_bound(max_new_tokens)
+            self._backend_check(sampling)
         rid = self._next_id if request_id is None else request_id
         if not 0 <= rid < 2 ** 32:
             raise ValueError("request ids are uint32")
@@ -757,11 +848,18 @@ class SlotScheduler:
             raise ValueError(f"max_new_tokens {max_new_tokens} outside [1, {room}]")
         if sampling is not None:
             sampling.check_bound(max_new_tokens)
+            self._backend_check(sampling)
         del self.parked[request_id]
         r = _Request(request_id, n_new, c, max_new_tokens, payload, keep, past=length, sampling=sampling)
         r.slot = slot
         self.continuations.append(r)
         return request_id
+
+    def _backend_check(self, sampling) -> None:
+        """``backend.check_sampling(sampling)`` (optional) refuses, with ValueError, what the backend cannot serve."""
+        check = getattr(self.backend, "check_sampling", None)
+        if check is not None:
+            check(sampling)
 
     def release(self, request_id: int) -> None:
         """Free the slot of a parked request."""
@@ -908,15 +1006,26 @@ class ContinuousGenerator:
     owns one value of every control per slot and the bitmap of the tokens each slot has seen, sets them behind every
     admission and extension (ergm_sample_mark), and samples with ergm_sample_rows (ergm_decode_run_slots_sampled on the
     executor engines): still nothing is read back inside a chunk.  With ``controls=False`` every launch is the one
-    described above."""
+    described above.
+
+    Logit rules (``SamplingParams.no_repeat_ngram_size`` / ``bad_words_ids``, ``controls=True``): the generator keeps
+    the ordered tokens of every slot on the device (``hist`` int32 [max_batch, max_len]) beside one ``start`` / ``ngram``
+    value per slot and a pool row of ``bad_words_cap`` entries for its bad words (one per token and one per sequence).
+    They are written behind every admission and extension that carries a rule (ergm_hist_write), a new tenant inherits
+    nothing, a parked slot keeps its history, and while a ruled request is live every round bans before it samples and
+    records what it drew (ergm_logit_rules_apply, ergm_hist_append: two launches more; ergm_decode_set_rules on the
+    executor engines).  While none is live the rounds launch what they always did."""
 
     ENGINES = BatchedGenerator.ENGINES
 
     def __init__(self, model, max_batch: int, max_len: int, cap_max: int, engine: str = "python",
                  max_admit: Optional[int] = None, max_admit_tokens: Optional[int] = None, keep_logits: bool = False,
-                 controls: bool = False):
+                 controls: bool = False, bad_words_cap: int = 64):
         if engine not in self.ENGINES:
             raise ValueError(f"engine {engine!r} is not one of {sorted(self.ENGINES)}")
+        if isinstance(bad_words_cap, bool) or not isinstance(bad_words_cap, int) or bad_words_cap < 1:
+            raise ValueError(f"bad_words_cap {bad_words_cap!r} is not a positive integer")
+        self.bad_words_cap = bad_words_cap
         cfg = model.config
         if max_len > cfg.n_positions:
             raise ValueError(f"max_len {max_len} > n_positions {cfg.n_positions}")
@@ -959,6 +1068,15 @@ class ContinuousGenerator:
                                        min_step=self.min_step, seen=self.seen)
             self._slot_sp: List[Optional[SamplingParams]] = [None] * mb   # what each slot was last given
             self._lp_acc: List[Optional[list]] = [None] * mb              # the log-probabilities of the turn so far
+            # logit rules: the slots' token histories, start | ngram per slot, and the bad-word pool
+            self.hist = torch.zeros(mb, max_len, dtype=torch.int32, device=dev)
+            self._rule_vals = torch.zeros(2, mb, dtype=torch.int32, device=dev)
+            self._bad_pool = torch.zeros(mb, bad_words_cap, dtype=torch.int32, device=dev)
+            self._rules = ops.rules_desc(self.hist, start=self._rule_vals[0], ngram=self._rule_vals[1], bad=self._bad_pool)
+            self._slot_ruled = [False] * mb    # the slot's device values hold a rule and its history is kept
+            self._rule_live = [False] * mb     # ... and a request is running in it
+            self._rules_bound = False          # the executor plan holds the rules (ergm_decode_set_rules)
+            self._hist_host: List[list] = [[] for _ in range(mb)]   # what each slot's cache holds, as segments
         if engine != "python":
             self._create_plan()
 
@@ -1023,14 +1141,57 @@ class ContinuousGenerator:
                 old = None if slots is None else self._slot_sp[slots[b]]
                 sampling[b] = SamplingParams() if old is None else replace(old, min_new_tokens=0)
             sampling[b].check_bound(max_new[b])
+            self.check_sampling(sampling[b])
             if sampling[b].top_p is None and self._sampling is None:
                 raise ValueError("top_p=None takes the run's top_p: outside run / drain give the request its own")
         return sampling
 
-    def _set_controls(self, slots, sps, ids, q0, lens, reset: bool) -> None:
+    def _set_rules(self, slots, sps, ids, q0, lens, past) -> None:
+        """The slots' rule values (start, ngram, the bad-word pool row) and their token histories, behind the admission
+        or extension that filled them: one copy to the device, two scatters, one ergm_hist_write of the new ids at
+        ``past``.  A slot that carried no rule so far has no history on the device: its earlier tokens are written
+        from the host's record (a second ergm_hist_write)."""
+        rows, late = [], []
+        for b, (s, sp) in enumerate(zip(slots, sps)):
+            direct = past[b] == 0 or self._slot_ruled[s] or not sp.has_rules
+            if not direct:
+                late.append(b)
+            start = past[b] + lens[b] if sp.no_repeat_scope == "turn" else 0
+            rows.append([s, q0[b], lens[b] if direct else 0, past[b], start, sp.no_repeat_ngram_size,
+                         *pack_bad_words(sp.bad_words_ids, self.bad_words_cap)])
+        m = torch.tensor(rows, dtype=torch.int32).to(self.dev)
+        sl = m[:, 0].long()
+        self._rule_vals[:, sl] = m[:, 4:6].t()
+        self._bad_pool[sl] = m[:, 6:]
+        w = m[:, :4].t().contiguous()
+        ops.hist_write(ids, w[0], w[1], w[2], self.hist, self.max_len, pos0=w[3])
+        if late:
+            full = []
+            for b in late:
+                seq = [int(t) for seg in self._hist_host[slots[b]] for t in (seg.tolist() if torch.is_tensor(seg) else seg)]
+                if len(seq) != past[b] + lens[b]:
+                    raise ValueError(f"slot {slots[b]}: a rule that starts in a later turn needs the slot's earlier tokens, "
+                                     "which are known for requests served by run / drain only: give the rule at admission")
+                full.append(seq)
+            q = [sum(len(x) for x in full[:i]) for i in range(len(full))]
+            w = torch.tensor([[slots[b] for b in late], q, [len(x) for x in full]], dtype=torch.int32).to(self.dev)
+            flat = torch.tensor([t for x in full for t in x], dtype=torch.int64).to(self.dev)
+            ops.hist_write(flat, w[0], w[1], w[2], self.hist, self.max_len)
+        for s, sp in zip(slots, sps):
+            self._slot_ruled[s] = self._rule_live[s] = sp.has_rules
+
+    def _set_controls(self, slots, sps, ids, q0, lens, reset: bool, past=None, segs=None) -> None:
         """The slots' control values, their bitmap rows (cleared first at an admission) and their minimum length, behind
-        the admission or extension that filled them: one copy to the device, one scatter, one ergm_sample_mark."""
+        the admission or extension that filled them: one copy to the device, one scatter, one ergm_sample_mark; then the
+        logit rules of the slots that carry one or carried one (``_set_rules``)."""
         n_seq = len(slots)
+        past = [0] * n_seq if past is None else past
+        for b, s in enumerate(slots):   # the host's record of what the slot's cache holds
+            if reset:
+                self._hist_host[s] = []
+            self._hist_host[s].append(segs[b])
+        if any(sp.has_rules for sp in sps) or any(self._slot_ruled[s] for s in slots):
+            self._set_rules(slots, sps, ids, q0, lens, past)
         top_p = [self._sampling[0] if sp.top_p is None else sp.top_p for sp in sps]
         f = torch.tensor([top_p, [sp.temperature for sp in sps], [sp.repetition_penalty for sp in sps]], dtype=torch.float32)
         i = torch.tensor([[sp.top_k for sp in sps], slots, q0, lens, [int(reset)] * n_seq,
@@ -1080,7 +1241,8 @@ class ContinuousGenerator:
         else:
             self._admit_native(slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has)
         if sps is not None:   # behind the admission: it set row_steps, which the minimum length counts from
-            self._set_controls(slots, sps, torch.cat(ids_l).to(device=self.dev, dtype=torch.int64), q0, lens, reset=True)
+            self._set_controls(slots, sps, torch.cat(ids_l).to(device=self.dev, dtype=torch.int64), q0, lens, reset=True,
+                               segs=ids_l)
 
     def _packed_python(self, ids_l, tt_l, cap_l, lens, clens, q0, c0, vis, aud, has, keep_kv=None, keep_ckv=None):
         """The packed rows of n_seq sequences through the embedding and every block with the per-sequence kernels of the
@@ -1292,7 +1454,7 @@ class ContinuousGenerator:
         else:
             self._extend_native(slots, ids, tt, pos, lens, past, clens, q0, max_new)
         if sps is not None:
-            self._set_controls(slots, sps, ids, q0, lens, reset=False)
+            self._set_controls(slots, sps, ids, q0, lens, reset=False, past=past, segs=ids_l)
 
     def _extend_python(self, slots, ids, tt, pos, lens, past, clens, q0, max_new) -> None:
         """The yardstick: the row-wise kernels over the packed rows, the K | V rows copied by torch, and the attention
@@ -1377,7 +1539,11 @@ class ContinuousGenerator:
         lp = None
         if self.controls and any(a is not None for a in self._lp_acc):
             lp = torch.zeros(n, B, dtype=torch.float32, device=self.dev)
+        ruled = self.controls and any(self._rule_live)   # some live request carries a logit rule
         if self.engine != "python":
+            if self.controls and ruled != self._rules_bound:
+                L.call("ergm_decode_set_rules", self._plan, C.byref(self._rules) if ruled else None)
+                self._rules_bound = ruled
             if self.controls:
                 L.call("ergm_decode_run_slots_sampled", self._plan, n, float(top_p), C.byref(self._ctl), seed & (2 ** 64 - 1),
                        eos_id, sp2_id, C.c_void_p(out.data_ptr()), None if lp is None else C.c_void_p(lp.data_ptr()),
@@ -1390,8 +1556,12 @@ class ContinuousGenerator:
             V = self.m.layout.vocab
             for i in range(n):
                 if self.controls:
+                    if ruled:
+                        ops.logit_rules(self._logits, V, self._rules, self.lens, eos_id, self.max_len, finished=self.finished)
                     ops.sample_rows(self._logits, V, top_p, seed, self.row_ids, self.row_steps, eos_id, ctl=self._ctl,
                                     finished=self.finished, tokens=out[i], logprob=None if lp is None else lp[i])
+                    if ruled:
+                        ops.hist_append(out[i], self.lens, self.hist, self.max_len, finished=self.finished)
                 else:
                     ops.topp_sample_rows(self._logits, V, top_p, seed, self.row_ids, self.row_steps, eos_id,
                                          finished=self.finished, tokens=out[i])
@@ -1421,13 +1591,24 @@ class ContinuousGenerator:
         if self.controls and self._lp_acc[slot] is not None:   # the chunk ran on past the request's last token
             self.token_logprobs[request.id] = self._lp_acc[slot][:len(request.tokens)]
             self._lp_acc[slot] = None
+        if self.controls:   # an eos that was drawn is never stepped into the cache, nor into the history
+            toks = request.tokens
+            self._hist_host[slot].append(toks[:-1] if toks and toks[-1] == self._sampling[1] else list(toks))
+            self._rule_live[slot] = False
 
     # ---- requests -----------------------------------------------------------------------------------------
-    def _check_sampling(self, sampling) -> None:
+    def check_sampling(self, sampling) -> None:
+        """ValueError for what this generator cannot serve: any ``sampling`` without ``controls=True``, bad words that do
+        not fit a pool row of ``bad_words_cap`` entries, a rule with a cache longer than the 1,024 positions the rule
+        kernel stages.  The scheduler calls it at ``submit`` / ``extend``, the low-level ``admit`` / ``extend`` too."""
         if sampling is not None and not self.controls:
             raise ValueError("sampling parameters need ContinuousGenerator(controls=True)")
         if sampling is not None and not isinstance(sampling, SamplingParams):
             raise ValueError("sampling must be a SamplingParams")
+        if sampling is not None and sampling.has_rules:
+            pack_bad_words(sampling.bad_words_ids, self.bad_words_cap)
+            if self.max_len > 1024:
+                raise ValueError(f"logit rules need max_len <= 1024 (it is {self.max_len})")
 
     def submit(self, prompt, max_new_tokens: Optional[int] = None, request_id: Optional[int] = None,
                keep: bool = False, sampling: Optional[SamplingParams] = None) -> int:
@@ -1436,7 +1617,7 @@ class ContinuousGenerator:
         prompt that carries visual / audio features has at least 2 tokens (the positions the features sit at)."""
         if keep and prompt[3] is not None and int(prompt[0].numel()) < 2:
             raise ValueError("a kept prompt with visual / audio features needs at least 2 tokens")
-        self._check_sampling(sampling)
+        self.check_sampling(sampling)
         return self.sched.submit(int(prompt[0].numel()), int(prompt[2].numel()), max_new_tokens, request_id, prompt, keep,
                                  sampling=sampling)
 
@@ -1451,7 +1632,7 @@ class ContinuousGenerator:
         ids, token_types = ids.reshape(-1), token_types.reshape(-1)
         if ids.numel() != token_types.numel():
             raise ValueError("one token type per token")
-        self._check_sampling(sampling)
+        self.check_sampling(sampling)
         return self.sched.extend(request_id, int(ids.numel()), max_new_tokens, (ids, token_types), keep, sampling=sampling)
 
     def release(self, request_id: int) -> None:

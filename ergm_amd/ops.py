@@ -662,6 +662,69 @@ def beam_gather(caches, parent, lens, W: int, max_len: Optional[int] = None):
            _ptr(lens), R, W, rows, _stream(c0.device))
 
 
+def rules_desc(hist, start=None, ngram=None, bad=None) -> L.LogitRules:
+    """ergm_logit_rules over device tensors: hist int32 [R, >= max_len] (rows ld_hist apart), start / ngram int32 [R],
+    bad int32 [R, ld_bad] (length-prefixed sequences); None turns a rule off.  The struct holds addresses only: the
+    caller keeps the tensors alive."""
+    _need_gpu(hist)
+    assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.stride(1) == 1
+    for t in (start, ngram):
+        if t is not None:
+            _need_gpu(t)
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= hist.shape[0]
+    if bad is not None:
+        _need_gpu(bad)
+        assert bad.dtype == torch.int32 and bad.dim() == 2 and bad.stride(1) == 1 and bad.shape[0] >= hist.shape[0]
+    p = lambda t: None if t is None else t.data_ptr()
+    return L.LogitRules(p(hist), hist.stride(0), p(start), p(ngram), p(bad), 0 if bad is None else bad.stride(0))
+
+
+def logit_rules(logits, V: int, rules: L.LogitRules, lens, eos_id: int, max_len: int, finished=None):
+    """Ban the tokens the rows' rules forbid next, in place (ergm_logit_rules_apply): logits f32 [R, >= V], ``rules``
+    from ``rules_desc``, lens int32 [R], finished uint8 [R] or None.  A banned token's logit becomes -inf; eos_id never."""
+    _need_gpu(logits, lens)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() >= logits.shape[0]
+    assert finished is None or (finished.dtype == torch.uint8 and finished.is_contiguous())
+    L.call("ergm_logit_rules_apply", _ptr(logits), logits.stride(0), logits.shape[0], V, C.byref(rules), _ptr(lens),
+           _ptr(finished), eos_id, max_len, _stream(logits.device))
+    return logits
+
+
+def hist_write(ids, slot, start, length, hist, max_len: int, pos0=None, n_slots: Optional[int] = None):
+    """The packed ``ids`` (int64 [total]) of n_seq sequences into the history rows of their slots (ergm_hist_write):
+    slot / start / length (and pos0, the first position written; None: 0) int32 [n_seq] on the device, hist int32
+    [n_slots, >= max_len]."""
+    _need_gpu(ids, slot, start, length, hist)
+    assert ids.dtype == torch.int64 and ids.is_contiguous()
+    for t in (slot, start, length, pos0):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() == slot.numel())
+    assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.stride(1) == 1
+    L.call("ergm_hist_write", _ptr(ids), ids.numel(), _ptr(slot), _ptr(start), _ptr(length), _ptr(pos0), slot.numel(),
+           hist.shape[0] if n_slots is None else n_slots, _ptr(hist), hist.stride(0), max_len, _stream(ids.device))
+
+
+def hist_append(tokens, lens, hist, max_len: int, finished=None):
+    """hist[r, lens[r]] = tokens[r] for every row that is not finished (ergm_hist_append): tokens int64 [R], lens int32
+    [R], finished uint8 [R] or None; behind the sampler or the select, before the step."""
+    _need_gpu(tokens, lens, hist)
+    assert tokens.dtype == torch.int64 and tokens.is_contiguous() and lens.dtype == torch.int32 and lens.is_contiguous()
+    assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.stride(1) == 1 and hist.shape[0] >= tokens.numel()
+    assert finished is None or (finished.dtype == torch.uint8 and finished.is_contiguous())
+    L.call("ergm_hist_append", _ptr(tokens), _ptr(lens), _ptr(finished), tokens.numel(), _ptr(hist), hist.stride(0), max_len,
+           _stream(tokens.device))
+
+
+def hist_follow(hist, parent, lens, W: int, max_len: int):
+    """The histories follow the beams (ergm_hist_follow): the rows ``beam_gather`` moves for ``parent`` take positions
+    [0, lens[parent[r]]) of their parent's row.  lens is not written."""
+    _need_gpu(hist, parent, lens)
+    assert parent.dtype == torch.int32 and lens.dtype == torch.int32 and parent.is_contiguous() and lens.is_contiguous()
+    assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.stride(1) == 1 and hist.shape[0] >= parent.numel()
+    L.call("ergm_hist_follow", _ptr(hist), hist.stride(0), _ptr(parent), _ptr(lens), parent.numel(), W, max_len,
+           _stream(hist.device))
+
+
 def feat_pool(x: torch.Tensor, lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """Mean over frames of encoder outputs x [B, T, D] (f32 / bf16, any row strides with unit
     last-dim stride) -> [B, D] f32; ``lengths`` [B] int32 limits each sample to its valid frames.

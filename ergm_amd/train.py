@@ -107,7 +107,8 @@ class Trainer:
 
     @torch.no_grad()
     def test(self, loader, top_p: float, eos_id: int, sp2_id: int, seed: int = 0, max_batch: int = 8,
-             max_len: Optional[int] = None, engine: str = "python", sampling=None, num_beams: Optional[int] = None):
+             max_len: Optional[int] = None, engine: str = "python", sampling=None, num_beams: Optional[int] = None,
+             no_repeat_ngram_size: int = 0, no_repeat_scope: str = "sequence", bad_words_ids=()):
         """The reference's ``test()`` (src/main.py:291-335) without the tokenizer: one sampled response for every
         sample of ``loader``, all of them served by one ``ContinuousGenerator`` of ``max_batch`` slots.  A sample's
         prompt is its first n tokens, n = the count of tokens that are not ``eos_id`` (the collate pads with eos), with
@@ -117,7 +118,9 @@ class Trainer:
         to text is the caller's.  ``sampling``: one ``SamplingParams`` for every sample (None: plain
         top-p, the sampler and the launches of before).  ``num_beams`` = W: the best hypothesis of a beam search of W
         beams instead of a sample (``BatchedGenerator.beam_search`` in static batches of ``max_batch // W`` prompts;
-        ``top_p``, ``seed`` and ``sampling`` are not used); None is the sampled path, unchanged."""
+        ``top_p``, ``seed`` and ``sampling`` are not used); None is the sampled path, unchanged.
+        ``no_repeat_ngram_size`` / ``no_repeat_scope`` / ``bad_words_ids`` go to the beam search (the sampled path
+        carries them in ``sampling``)."""
         from .generate import BatchedGenerator, ContinuousGenerator
         self.model.eval()
         dev = self.device
@@ -138,6 +141,8 @@ class Trainer:
             return [], [], [], []
         if max_len is None:
             max_len = self.model.config.n_positions
+        if num_beams is None and (no_repeat_ngram_size or bad_words_ids):
+            raise ValueError("without num_beams the logit rules travel in sampling (SamplingParams)")
         if num_beams is not None:
             if sampling is not None:
                 raise ValueError("num_beams and sampling exclude each other")
@@ -147,7 +152,9 @@ class Trainer:
             beams = BatchedGenerator(self.model, max_batch=max_batch, max_len=max_len, engine=engine)
             hyps = []
             for i in range(0, len(prompts), per):
-                hyps += [h[0][0] for h in beams.beam_search(prompts[i:i + per], num_beams, eos_id, sp2_id)]
+                hyps += [h[0][0] for h in beams.beam_search(prompts[i:i + per], num_beams, eos_id, sp2_id,
+                                                          no_repeat_ngram_size=no_repeat_ngram_size,
+                                                          no_repeat_scope=no_repeat_scope, bad_words_ids=bad_words_ids)]
             return hyps, refs, emos, [float(x) for x in torch.stack(losses).tolist()]
         gen = ContinuousGenerator(self.model, max_batch=max_batch, max_len=max_len,
                                   cap_max=max(int(p[2].numel()) for p in prompts), engine=engine,

@@ -31,6 +31,8 @@
  *   ergm_beam_select, ergm_beam_gather, ergm_decode_run_beams (same version)
  *                         beam search over the same caches: the cache reordering of _reorder_cache
  *                         (src/model.py:739-746) and the ranking in front of it, on the device
+ *   ergm_logit_rules_apply, ergm_hist_write, ergm_hist_append, ergm_hist_follow, ergm_decode_set_rules (same version)
+ *                         no_repeat_ngram_size and bad_words_ids of generation, over a token history on the device
  *   ergm_linear_rows      Conv1D / lm_head for the few rows of a decode step, with the nn.LayerNorm in front
  *                         of it (src/model.py:298,318,332) computed in the same launch
  *   ergm_decode_*         the token loop of nucleus_sampling (src/main.py:253-282) for a batch, after the
@@ -915,6 +917,75 @@ int ergm_beam_gather(void* const* caches, int n_layer, int64_t ld_seq, int64_t l
                      int* lens, int R, int W, int max_len, void* stream);
 int ergm_decode_run_beams(ergm_decode_plan* plan, int n, int W, int64_t eos_id, int64_t sp2_id, float* scores,
                           int64_t* tokens_out, int* parents_out, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- Logit rules: no repeated n-gram, bad words (found by symbol, ABI unchanged) ------------------------------------
+ * Both rules need the ordered tokens of a row, which no other kernel keeps: hist is int32 [R][ld_hist], row r holding
+ * the prompt and the generated tokens of the sequence in row r at their sequence positions.  For a row r:
+ *     L  = clamp(lens[r], 0, max_len)           h[0 .. L) = hist[r][0 .. L)
+ *     s0 = clamp(start[r], 0, L)                n = ngram[r]
+ * No-repeat n-gram.  Off for n < 1 or n > ERGM_NGRAM_MAX; nothing is banned while L - s0 < n - 1.  Otherwise, with the
+ * tail t = h[L-n+1 .. L-1] (empty for n = 1): for every i with s0 <= i and i + n - 1 <= L - 1 such that
+ * h[i .. i+n-2] == t, the token h[i+n-1] is banned.  Only n-grams that lie wholly inside [s0, L) count; for n = 1
+ * every token of h[s0 .. L) is banned.  This is Hugging Face's NoRepeatNGramLogitsProcessor over [s0, L).
+ * Bad words.  bad is int32 [R][ld_bad]; a row is a run of sequences, each a length m followed by its m tokens
+ * w_0 .. w_{m-1}, 1 <= m <= ERGM_NGRAM_MAX.  The run ends at a length outside [1, ERGM_NGRAM_MAX] (0 is the usual
+ * terminator), at a sequence the pool cuts off (its last token would lie at or past ld_bad), or at ld_bad.  The token
+ * w_{m-1} is banned when m - 1 <= L and h[L-m+1 .. L-1] == w[0 .. m-2]: the match runs over the whole history, not
+ * from s0, and a one-token sequence is always banned.
+ * Both.  A banned token j with 0 <= j < V and j != eos_id gets logits[r][j] = -inf.  eos_id is never banned, so a
+ * sequence can always end.  History entries and list tokens outside [0, V) ban nothing and match nothing but
+ * themselves (the compares are on the int32 values).  Logits are never read; columns >= V, rows with both rules off
+ * and rows whose finished flag is set are not touched, bit for bit.  start, ngram and bad may each be NULL: off (s0 =
+ * 0).  lens, start, ngram and the list contents are device data and may hold anything: every value is clamped or
+ * compared as above before it forms an address.  One workgroup per row, the history staged in LDS; a ban is a plain
+ * 4-byte store of one value, so there are no atomics and every run gives the same bits, and applying twice equals
+ * applying once.
+ * Consumers.  ergm_sample_rows and ergm_beam_select treat -inf as "no mass / no candidate", so the ban precedes every
+ * other step of the sampler (the penalty, the minimum length, ...) and the returned logprob is under the distribution
+ * renormalised over the tokens still allowed.  A beam candidate's value is likewise normalised over the tokens its
+ * beam may still take: this deviates from Hugging Face, which masks after the log-softmax and so keeps the banned
+ * tokens' mass in the denominator.  A row in which every token with mass is banned (n = 1 with a history that covers
+ * the vocabulary but for eos, whose own mass floors to 0) is the caller's problem: the sampler then falls back as it
+ * does for any row without mass (it returns a token inside [0, V), ergm_sample_rows), a beam offers no candidate and
+ * ergm_beam_select ends the rows it cannot fill (score -inf, finished, eos_id).  No index leaves a table.
+ * ERGM_EINVAL before any launch: a NULL logits / rules / lens / hist, R outside [1, 65,535], V outside [1, 53,248]
+ * (the sampler's bound), ldl < V, max_len outside [1, 1,024], ld_hist < max_len, eos_id outside [0, V), bad with
+ * ld_bad < 1.  With ngram and bad both NULL nothing is launched.
+ *
+ * History upkeep.  ergm_hist_write: the packed ids of an admission or an extension (ergm_sample_mark's slot / start /
+ * len over device int64 ids [total], clamped the same way) go to hist[slot[b]][pos0[b] ..), pos0 (device int [n_seq],
+ * NULL: 0) clamped to [0, max_len] and the length to what is left before max_len; a slot outside [0, n_slots) writes
+ * nothing; an id that is no int32 is stored as -1.  ergm_hist_append: a row that is not finished (finished may be
+ * NULL) records tokens[r] at hist[r][lens[r]] when 0 <= lens[r] < max_len: called behind the sampler or the select and
+ * before the step advances the length.  ergm_hist_follow: for every row that ergm_beam_gather moves (parent[r] != r,
+ * parent[r] in the row's own group and keeping its own row), positions [0, clamp(lens[parent[r]], 0, max_len)) of row
+ * parent[r] go to row r; sources keep their row, so the copy is safe in place, and lens is not written (it may run
+ * before or behind the gather).
+ *
+ * ergm_decode_set_rules(plan, rules): the struct is copied, NULL turns the rules off (works on an unbound plan;
+ * ERGM_EINVAL for a NULL hist, ld_hist < the plan's max_len or a max_len above 1,024).  While set,
+ * ergm_decode_run_slots_sampled runs ergm_logit_rules_apply over all slots before each ergm_sample_rows and
+ * ergm_hist_append behind it (2 launches more per round), and ergm_decode_run_beams runs ergm_logit_rules_apply before
+ * each select and ergm_hist_follow, ergm_hist_append behind the gather (3 more).  When not set both enqueue what they
+ * always did; the caller, who knows whether any occupied row has a rule, sets and clears it.                        */
+#define ERGM_NGRAM_MAX 8
+typedef struct {
+    int32_t* hist;       /* [R][ld_hist] */
+    int ld_hist;
+    const int* start;    /* [R] s0, NULL: 0 */
+    const int* ngram;    /* [R] n, NULL: the n-gram rule is off */
+    const int32_t* bad;  /* [R][ld_bad] length-prefixed sequences, NULL: no bad words */
+    int ld_bad;
+} ergm_logit_rules;
+int ergm_logit_rules_apply(float* logits, int ldl, int R, int V, const ergm_logit_rules* rules, const int* lens,
+                           const uint8_t* finished, int64_t eos_id, int max_len, void* stream);
+int ergm_hist_write(const int64_t* ids, int total, const int* slot, const int* start, const int* len, const int* pos0,
+                    int n_seq, int n_slots, int32_t* hist, int ld_hist, int max_len, void* stream);
+int ergm_hist_append(const int64_t* tokens, const int* lens, const uint8_t* finished, int R, int32_t* hist, int ld_hist,
+                     int max_len, void* stream);
+int ergm_hist_follow(int32_t* hist, int ld_hist, const int* parent, const int* lens, int R, int W, int max_len,
+                     void* stream);
+int ergm_decode_set_rules(ergm_decode_plan* plan, const ergm_logit_rules* rules);
 
 /* ---- Scoring given tokens (found by symbol, ABI unchanged) ---------------------------------------------------------
  * ergm_lm_score: the tied LM head and the log-softmax of R rows in one pass; no logits are written.  For row r and the

@@ -39,6 +39,11 @@ and ``sample``: the sampler launch alone at B = 32, V = 50,257 on the logits an 
 microseconds per launch in back-to-back windows of 200, the variants alternating inside every repeat: ergm_topp_sample_rows
 (old), ergm_sample_rows with no controls (defaults), top_k=50 only, repetition_penalty=1.2 only (the prompt's ids seen),
 and everything (top_k=50, temperature=0.8, repetition_penalty=1.2).
+Logit rules: the same 256 requests with controls=True and, on every request,
+  br32/nr32/fr32  no_repeat_ngram_size=3          bw32/nw32/fw32  8 one-token bad words
+against bd32/nd32/fd32 (controls only, the launches of before) in one ``--cases`` list, alternating.  The rules need an
+eos inside the vocabulary, so these cases run with BEAM_EOS and count the tokens they produced.  ``--beams W --rules``
+adds the ruled beam_search calls (n = 3; 8 one-token bad words) to the alternation of ``--beams W``.
 Beam search, ``--beams W`` (W = 4 and W = 1 are recorded): G·W = 32 rows, 64 + 64 tokens, per engine the
 milliseconds of one beam_search call beside one generate() call at B = 32 (alternating in one process; generate() and
 everything under it are the parent commit's code, which the feature does not touch), the cache bytes the gather moved
@@ -61,12 +66,14 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 ENGINES = {"b": "python", "n": "native", "f": "fused"}
 CASES = {"kv": 240, **{e + b: 240 for e in ENGINES for b in ("1", "8", "32")}, "attn": 240,   # seconds a child may take
-         **{e + m + "32": 300 for e in ENGINES for m in "scdx"}, "admit": 240, "turns": 420, "sample": 240}
+         **{e + m + "32": 300 for e in ENGINES for m in "scdxrw"}, "admit": 240, "turns": 420, "sample": 240}
 N_REQ, REQ_MEAN = 256, 16
 PROMPT = CAPS = NEW = 64
 TOP_P, NO_EOS, SP2 = 0.95, -1, 50259
 REPEATS = 5
 EVERYTHING = dict(top_k=50, temperature=0.8, repetition_penalty=1.2)   # the controls of the x cases
+BAD_WORDS = [[1000 * i + 7] for i in range(1, 9)]                      # the w cases: 8 one-token bad words
+RULES = {"r": dict(no_repeat_ngram_size=3), "w": dict(bad_words_ids=BAD_WORDS)}
 
 
 def _event_ms(fn):
@@ -144,14 +151,21 @@ def _requests(case):
                 steps[0] += k - 1
     else:
         gen = ContinuousGenerator(model, max_batch=B, max_len=PROMPT + NEW, cap_max=CAPS, engine=engine,
-                                  controls=case[1] in "dx")
-        sampling = {"c": None, "d": SamplingParams(), "x": SamplingParams(**EVERYTHING)}[case[1]]
+                                  controls=case[1] in "dxrw")
+        sampling = {"c": None, "d": SamplingParams(), "x": SamplingParams(**EVERYTHING),
+                    **{k: SamplingParams(**v) for k, v in RULES.items()}}[case[1]]
+        ruled = case[1] in RULES
+        produced = [sum(new)]
 
         def run():
             s0, a0 = gen.sched.steps, gen.admit_calls
-            out = gen.generate(prompts, top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2, seed=7, max_new_tokens=new,
-                               sampling=sampling)
-            assert [len(r) for r in out] == new
+            out = gen.generate(prompts, top_p=TOP_P, eos_id=BEAM_EOS if ruled else NO_EOS, sp2_id=SP2, seed=7,
+                               max_new_tokens=new, sampling=sampling)
+            if ruled:   # an eos inside the vocabulary can be drawn: count what came out
+                assert all(1 <= len(r) <= m for r, m in zip(out, new))
+                produced[0] = sum(len(r) for r in out)
+            else:
+                assert [len(r) for r in out] == new
             steps[0], admits[0] = gen.sched.steps - s0, gen.admit_calls - a0
     run()
     ms = [_event_ms(run) for _ in range(REPEATS)]
@@ -160,7 +174,8 @@ def _requests(case):
                       "max_new_mean": round(sum(new) / N_REQ, 2), "max_new_max": max(new), "decode_steps": steps[0],
                       "steps_per_token": round(steps[0] / sum(new), 4),
                       "admit_calls": admits[0], "ms_median": round(med, 2),
-                      "ms_all": [round(x, 2) for x in ms], "tokens_per_s": round(sum(new) / med * 1e3, 1)}), flush=True)
+                      "ms_all": [round(x, 2) for x in ms], "produced_tokens": produced[0],
+                      "tokens_per_s": round(produced[0] / med * 1e3, 1)}), flush=True)
 
 
 def _admission():
@@ -330,8 +345,16 @@ def _beams(W):
             out = gen_p.generate(prompts, top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2, seed=7, max_new_tokens=NEW)
             assert all(len(r) == NEW for r in out)
         ms = {"beam": [], "plain": []}
+        fns = [("beam", beam), ("plain", plain)]
+        if "--rules" in sys.argv:
+            for key, kw in RULES.items():
+                def ruled(kw=kw):
+                    out = gen_b.beam_search(prompts[:G], W, BEAM_EOS, SP2, max_new_tokens=NEW, **kw)
+                    assert all(1 <= len(h[0][0]) <= NEW for h in out)
+                fns.append(("beam_" + key, ruled))
+                ms["beam_" + key] = []
         for rep in range(REPEATS + 1):   # alternating; the first of each is the warm-up
-            for name, fn in (("beam", beam), ("plain", plain)):
+            for name, fn in fns:
                 t = _event_ms(fn)
                 if rep:
                     ms[name].append(t)
@@ -342,6 +365,8 @@ def _beams(W):
                  for i, par in enumerate(parents)]
         print(json.dumps({"case": "beams", "select": mode, "engine": engine, "W": W, "G": G, "new_tokens": NEW,
                           "beam_ms_median": round(statistics.median(ms["beam"]), 2), "beam_ms_all": [round(x, 2) for x in ms["beam"]],
+                          **{k + "_ms_median": round(statistics.median(v), 2) for k, v in ms.items() if k.startswith("beam_")},
+                          **{k + "_ms_all": [round(x, 2) for x in v] for k, v in ms.items() if k.startswith("beam_")},
                           "generate_ms_median": round(statistics.median(ms["plain"]), 2),
                           "generate_ms_all": [round(x, 2) for x in ms["plain"]],
                           "gather_bytes_round0": moved[0], "gather_bytes_per_round_mean_later": round(sum(moved[1:]) / (NEW - 1)),
@@ -425,7 +450,8 @@ def main():
         if "--child" in sys.argv:
             return _beams(W)
         for mode in ("two", "one", "two", "one"):   # the two forms of select, alternating, a fresh process each
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--beams", str(W), "--child"], timeout=420,
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--beams", str(W), "--child",
+                                *(["--rules"] if "--rules" in sys.argv else [])], timeout=420,
                                env={**os.environ, "ERGM_BEAM_SELECT": mode})
             if r.returncode != 0:
                 raise SystemExit(f"--beams {W} (select {mode}) failed with status {r.returncode}: stopping")
@@ -442,7 +468,7 @@ def main():
             _turns()
         elif case == "sample":
             _sampler()
-        elif len(case) == 4 and case[1] in "scdx":
+        elif len(case) == 4 and case[1] in "scdxrw":
             _requests(case)
         else:
             _generation(case)
