@@ -159,6 +159,8 @@ _SIGS = {
     "ergm_beam_select": (i32, [vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
     "ergm_beam_gather": (i32, [C.POINTER(vp), i32, i64, i64, i32, vp, vp, i32, i32, i32, vp]),
     "ergm_decode_run_beams": (i32, [vp, i32, i32, i64, i64, vp, vp, vp, vp, sz, vp]),
+    "ergm_beam_seed": (i32, [C.POINTER(vp), i32, i64, i64, i32, vp, C.POINTER(i32), i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "ergm_decode_run_slot_beams": (i32, [vp, i32, i32, i32, i64, i64, vp, vp, vp, vp, sz, vp]),
     "ergm_logit_rules_apply": (i32, [vp, i32, i32, i32, C.POINTER(LogitRules), vp, vp, i64, i32, vp]),
     "ergm_hist_write": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, vp, i32, i32, vp]),
     "ergm_hist_append": (i32, [vp, vp, vp, i32, vp, i32, i32, vp]),

@@ -9,6 +9,9 @@
 // as one (a workgroup per group that walks its W rows, the candidates in LDS): ERGM_BEAM_SELECT=one / two chooses, for
 // the measurement; both give the same bits, every comparison is on f32 values and integers and nothing is accumulated
 // in floating point across threads.
+//
+// In slot mode (ContinuousGenerator(num_beams=W)) a prompt is admitted into row g·W of a group alone,
+// and ergm_beam_seed gives the group's other rows the caption K | V and the state round 0 starts from.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -264,6 +267,52 @@ __global__ __launch_bounds__(256) void beam_gather_kernel(BgLayers layers, int64
     }
 }
 
+// ---- seeding a group of slots (slot mode) ---------------------------------------------------------------------------
+// The per-row state of the groups an admission filled: thread (b, w) for row w of group groups[b].  Row g·W is the
+// admission's and only its score is written; the rows behind it read that row's caption length and bound, which
+// nothing here writes, so every row has one writer and one launch needs no ordering inside it.
+__global__ void beam_seed_state_kernel(const int* __restrict__ groups, int n_grp, int W, int G, int cap_max, int* lens,
+                                       int* cap_lens, int* stop_lens, uint8_t* __restrict__ finished,
+                                       float* __restrict__ scores) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_grp * W) return;
+    const int b = t / W, w = t - b * W;
+    const int g = groups[b];
+    if (g < 0 || g >= G) return;
+    const int r0 = g * W, r = r0 + w;
+    if (w == 0) {
+        scores[r0] = 0.f;
+        return;
+    }
+    cap_lens[r] = max(0, min(cap_lens[r0], cap_max));
+    stop_lens[r] = stop_lens[r0];
+    lens[r] = 0;
+    finished[r] = 0;
+    scores[r] = -INFINITY;
+}
+
+// Workgroup ((b, w), layer, chunk): caption rows [chunk·64, chunk·64 + 64) below cap_lens[g·W] of the layer from slot
+// g·W to slot g·W + w, w >= 1: the gather's layout, 16 bytes per lane, a wave per cache row.  The group id is checked
+// and the length clamped to [0, cap_max] before an address is formed.
+__global__ __launch_bounds__(256) void beam_seed_copy_kernel(BgLayers layers, int64_t ld_seq, int64_t ld_row, int row_bytes,
+                                                             const int* __restrict__ groups, const int* __restrict__ cap_lens,
+                                                             int W, int G, int cap_max) {
+    const int b = blockIdx.x / (W - 1), w = 1 + blockIdx.x % (W - 1);
+    const int g = groups[b];
+    if (g < 0 || g >= G) return;  // uniform over the workgroup
+    const int r0 = g * W;
+    const int n = max(0, min(cap_lens[r0], cap_max));
+    const int lane = threadIdx.x & 63;
+    const int i1 = min(n, (int)(blockIdx.z + 1) * BG_ROWS);
+    char* base = layers.p[blockIdx.y];
+    for (int i = blockIdx.z * BG_ROWS + (threadIdx.x >> 6); i < i1; i += 4) {
+        const char* s = base + (int64_t)r0 * ld_seq + (int64_t)i * ld_row;
+        char* d = base + (int64_t)(r0 + w) * ld_seq + (int64_t)i * ld_row;
+        for (int c = lane * 16; c < row_bytes; c += 64 * 16)
+            *reinterpret_cast<uint4*>(d + c) = *reinterpret_cast<const uint4*>(s + c);
+    }
+}
+
 // ERGM_BEAM_SELECT=one: the one-launch form; anything else, or unset: two launches
 static bool beam_select_one() {
     static const bool one = [] {
@@ -341,4 +390,43 @@ extern "C" int ergm_beam_gather(void* const* caches, int n_layer, int64_t ld_seq
                     l0 == 0 ? 1 : 0);
     }
     return check_launch("beam_gather");
+}
+
+extern "C" int ergm_beam_seed(void* const* xkv, int n_layer, int64_t ld_seq, int64_t ld_row, int row_bytes,
+                              const int* groups_dev, const int* groups, int n_grp, int W, int max_batch, int cap_max, int* lens,
+                              int* cap_lens, int* stop_lens, uint8_t* finished, float* scores, void* stream) {
+    ERGM_CHECK_ARG(xkv && groups_dev && groups && lens && cap_lens && stop_lens && finished && scores, "beam_seed: null argument");
+    ERGM_CHECK_ARG(W >= 1 && W <= BM_MAXW, "beam_seed: W %d outside [1, %d]", W, BM_MAXW);
+    ERGM_CHECK_ARG(max_batch > 0 && max_batch % W == 0, "beam_seed: max_batch %d is not a positive multiple of W %d", max_batch, W);
+    const int G = max_batch / W;
+    ERGM_CHECK_ARG(n_grp >= 1 && n_grp <= G, "beam_seed: n_grp %d outside [1, %d groups]", n_grp, G);
+    unsigned char seen[(1 << 16) / 8] = {};
+    ERGM_CHECK_ARG(G <= (1 << 16), "beam_seed: more than 65536 groups");
+    for (int b = 0; b < n_grp; ++b) {
+        const int g = groups[b];
+        ERGM_CHECK_ARG(g >= 0 && g < G, "beam_seed: group %d (entry %d) outside [0, %d)", g, b, G);
+        ERGM_CHECK_ARG(!(seen[g >> 3] & (1 << (g & 7))), "beam_seed: group %d named twice", g);
+        seen[g >> 3] |= (unsigned char)(1 << (g & 7));
+    }
+    ERGM_CHECK_ARG(n_layer >= 1 && cap_max >= 1, "beam_seed: bad shape n_layer %d cap_max %d", n_layer, cap_max);
+    ERGM_CHECK_ARG(row_bytes > 0 && row_bytes % 16 == 0 && ld_seq % 16 == 0 && ld_row % 16 == 0,
+                   "beam_seed: row_bytes and the strides (bytes) must be multiples of 16");
+    ERGM_CHECK_ARG(ld_row >= row_bytes && ld_seq >= (int64_t)(cap_max - 1) * ld_row + row_bytes,
+                   "beam_seed: stride shorter than the rows it spans");
+    for (int l = 0; l < n_layer; ++l)
+        ERGM_CHECK_ARG(xkv[l] && aligned16(xkv[l]), "beam_seed: layer %d cache pointer null or not 16-byte aligned", l);
+    const int chunks = cdiv(cap_max, BG_ROWS);
+    ERGM_CHECK_ARG(chunks <= 65535, "beam_seed: cap_max %d too large", cap_max);
+    hipStream_t s = as_stream(stream);
+    // the copies first: they read cap_lens[g·W] only, which the state kernel leaves alone
+    for (int l0 = 0; W > 1 && l0 < n_layer; l0 += BG_MAX_LAYERS) {
+        const int nl = std::min(BG_MAX_LAYERS, n_layer - l0);
+        BgLayers L{};
+        for (int l = 0; l < nl; ++l) L.p[l] = reinterpret_cast<char*>(xkv[l0 + l]);
+        ERGM_LAUNCH(beam_seed_copy_kernel, dim3(n_grp * (W - 1), nl, chunks), dim3(256), 0, s, L, ld_seq, ld_row, row_bytes, groups_dev,
+                    cap_lens, W, G, cap_max);
+    }
+    ERGM_LAUNCH(beam_seed_state_kernel, dim3(cdiv(n_grp * W, 256)), dim3(256), 0, s, groups_dev, n_grp, W, G, cap_max, lens, cap_lens,
+                stop_lens, finished, scores);
+    return check_launch("beam_seed");
 }

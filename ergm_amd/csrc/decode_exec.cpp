@@ -947,6 +947,53 @@ extern "C" int ergm_decode_run_slots_sampled(ergm_decode_plan* P, int n, float t
     return run_slots(P, "decode_run_slots_sampled", n, top_p, ctl ? ctl : &none, seed, eos_id, sp2_id, tokens_out, logprobs_out, stream);
 }
 
+// n rounds of beam search over all max_batch slots, W slots per group: ergm_decode_run_beams' round with the slot step
+// behind it, so a live row is finished by the device at the bound of its admission (ergm_hip.h has the rule).
+extern "C" int ergm_decode_run_slot_beams(ergm_decode_plan* P, int n, int W, int rows_bound, int64_t eos_id, int64_t sp2_id,
+                                          float* scores, int64_t* tokens_out, int* parents_out, void* workspace, size_t ws_bytes,
+                                          void* stream) {
+    ERGM_TRY(slots_ready(P, "decode_run_slot_beams"));
+    const ergm_decode_dims& d = P->d;
+    const int B = d.max_batch;
+    ERGM_CHECK_ARG(n >= 1, "decode_run_slot_beams: n %d < 1", n);
+    ERGM_CHECK_ARG(W >= 1 && W <= 8 && W <= d.vocab, "decode_run_slot_beams: W %d outside [1, 8] or above the vocabulary %d", W,
+                   d.vocab);
+    ERGM_CHECK_ARG(B % W == 0, "decode_run_slot_beams: max_batch %d is no multiple of W %d", B, W);
+    ERGM_CHECK_ARG(eos_id >= 0 && eos_id < d.vocab, "decode_run_slot_beams: eos_id %lld outside the vocabulary", (long long)eos_id);
+    ERGM_CHECK_ARG(rows_bound >= 0 && rows_bound <= d.max_len, "decode_run_slot_beams: rows_bound %d outside [0, max_len %d]",
+                   rows_bound, d.max_len);
+    ERGM_CHECK_ARG(scores && tokens_out && parents_out && workspace, "decode_run_slot_beams: null argument");
+    ERGM_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && (reinterpret_cast<uintptr_t>(scores) & 3) == 0 &&
+                       (reinterpret_cast<uintptr_t>(tokens_out) & 7) == 0 && (reinterpret_cast<uintptr_t>(parents_out) & 3) == 0,
+                   "decode_run_slot_beams: misaligned argument (workspace and tokens_out 8 bytes, scores and parents_out 4)");
+    ERGM_CHECK_ARG(ws_bytes >= ergm_beam_select_workspace_size(B, W), "decode_run_slot_beams: workspace %zu < %zu bytes", ws_bytes,
+                   ergm_beam_select_workspace_size(B, W));
+    hipStream_t s = as_stream(stream);
+    const int64_t kv_row = (int64_t)2 * d.n_embd * 2;  // bytes of a K | V row
+    ERGM_TRY(decode_fill_i64(P->tt, sp2_id, B, s));
+    for (int i = 0; i < n; ++i) {
+        int64_t* tok = tokens_out + (size_t)i * B;
+        int* par = parents_out + (size_t)i * B;
+        Walk w{false, "decode_run_slot_beams", s};
+        if (P->ruled)
+            ERGM_TRY(ergm_logit_rules_apply(P->logits, d.vocab_pad, B, d.vocab, &P->rules, P->lens, P->finished, eos_id, d.max_len, s));
+        if (w.on(beam_select_launches()))
+            ERGM_TRY(ergm_beam_select(P->logits, d.vocab_pad, B, W, d.vocab, scores, P->finished, eos_id, par, tok, workspace,
+                                      ws_bytes, s));
+        // the caller's bound on the live lengths, one more per round: the gather's grid covers the rows in use
+        const int rows = std::max(1, (int)std::min<int64_t>((int64_t)rows_bound + i, d.max_len));
+        if (w.on(beam_gather_launches(d.n_layer)))
+            ERGM_TRY(ergm_beam_gather(P->kv.data(), d.n_layer, (int64_t)d.max_len * kv_row, kv_row, (int)kv_row, par, P->lens, B, W, rows,
+                                      s));
+        if (P->ruled) {  // the histories follow the caches, then take the round's tokens
+            ERGM_TRY(ergm_hist_follow(P->rules.hist, P->rules.ld_hist, par, P->lens, B, W, d.max_len, s));
+            ERGM_TRY(ergm_hist_append(tok, P->lens, P->finished, B, P->rules.hist, P->rules.ld_hist, d.max_len, s));
+        }
+        ERGM_TRY(walk(P, w, P->engine, B, tok, P->tt));
+    }
+    return ERGM_OK;
+}
+
 extern "C" int ergm_decode_launches(const ergm_decode_plan* P, int engine) {
     ERGM_CHECK_ARG(P && engine >= 0 && engine < kEngines, "decode_launches: bad plan or engine %d", engine);
     Walk w{true, "decode_launches"};

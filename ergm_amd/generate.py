@@ -23,7 +23,8 @@ for the whole batch without a sort or a host round trip.  ``KVCacheGenerator`` i
 ``ContinuousGenerator`` serves a queue of requests on a fixed set of cache slots (in-flight batching): every step runs
 over all slots, a slot finishes on the device at eos or at the bound recorded when it was filled, and the host, looking
 once in 8 steps, retires the finished requests and prefills waiting ones into the free slots.  ``SlotScheduler`` is its
-host-only policy.
+host-only policy.  With ``num_beams`` the same generator serves beam-search requests, each in a group of slots
+(``BeamScheduler``: the same policy over groups).
 """
 from __future__ import annotations
 
@@ -728,11 +729,13 @@ class SamplingParams:
 
 
 class _Request:
-    __slots__ = ("id", "n", "c", "max_new", "payload", "tokens", "slot", "keep", "past", "sampling")
+    __slots__ = ("id", "n", "c", "max_new", "payload", "tokens", "slot", "keep", "past", "sampling", "rounds", "cols")
 
     def __init__(self, rid: int, n: int, c: int, max_new: int, payload, keep: bool = False, past: int = 0, sampling=None):
         self.id, self.n, self.c, self.max_new, self.payload = rid, n, c, max_new, payload
         self.tokens: List[int] = []
+        self.rounds = 0            # beam mode: the rounds run since the admission
+        self.cols: List[tuple] = []   # beam mode: per round, the group's (tokens, parents within the group)
         self.slot = NO_REQUEST
         self.keep = keep      # park the slot when the request ends
         self.past = past      # a continuation: the rows its slot already holds (n counts the new ones)
@@ -943,6 +946,79 @@ class SlotScheduler:
         return dict(self.drain(eos_id))
 
 
+class BeamScheduler(SlotScheduler):
+    """``SlotScheduler``'s policy over groups of ``num_beams`` slots (queue, FIFO admission under ``max_admit`` /
+    ``max_admit_tokens``, the least recently admitted free group first, a look every ``look`` rounds), for beam search
+    in slot mode.  What the scheduler calls a slot is a group here: group g owns rows g·W .. g·W + W - 1.
+
+    * ``backend.admit_requests(groups, requests)`` prefills each request into row g·W of its group and seeds the group;
+    * ``backend.run_beam_chunk(n)`` runs n select + gather + step rounds over every row and returns ``(tokens, parents,
+      finished, scores)``: n lists of one token / one parent row per row, one flag and one score per row, read back once;
+    * ``backend.retire(group, request)`` (optional) is told when a request leaves its group.
+
+    The host keeps a live group's (tokens, parents) columns from its admission round on.  A group retires at the first
+    look at which all its rows are finished on the device (eos on every beam, or the bound of the admission); the host
+    cross-checks that a group whose rounds reached ``max_new_tokens`` is finished.  A chunk runs on past a request's
+    bound (finished rows offer eos at unchanged scores), so the hypotheses are read back over exactly
+    ``min(rounds, max_new_tokens)`` rounds (``beam_backtrack``).  No sessions: ``keep`` and ``extend`` are refused."""
+
+    def __init__(self, backend, n_groups: int, num_beams: int, max_len: int, cap_max: int, max_admit: Optional[int] = None,
+                 max_admit_tokens: Optional[int] = None, look: int = 8):
+        if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
+            raise ValueError(f"num_beams {num_beams!r} outside [1, 8]")
+        super().__init__(backend, n_groups, max_len, cap_max, max_admit, max_admit_tokens, look)
+        self.num_beams = num_beams
+
+    def submit(self, n: int, c: int, max_new_tokens: Optional[int] = None, request_id: Optional[int] = None,
+               payload=None, keep: bool = False, sampling=None) -> int:
+        if keep:
+            raise ValueError("beam mode has no sessions (keep=True)")
+        return super().submit(n, c, max_new_tokens, request_id, payload, False, sampling)
+
+    def extend(self, *args, **kwargs) -> int:
+        raise ValueError("beam mode has no sessions (extend)")
+
+    def drain(self, eos_id: int, length_penalty: float = 1.0, num_return: int = 1):
+        """Run until nothing is queued and nothing is running, yielding (id, [(tokens, sum_logprob), ...]) of each
+        request as its group retires: ``beam_backtrack``'s result for the group."""
+        W = self.num_beams
+        if isinstance(num_return, bool) or not isinstance(num_return, int) or not 1 <= num_return <= W:
+            raise ValueError(f"num_return {num_return!r} outside [1, num_beams {W}]")
+        while self.queue or any(r is not None for r in self.live):
+            self._admit()
+            tokens, parents, finished, scores = self.backend.run_beam_chunk(self.look)
+            self.steps += self.look
+            for g, r in enumerate(self.live):
+                if r is None:
+                    continue
+                r0 = g * W
+                for trow, prow in zip(tokens, parents):
+                    par = [int(p) - r0 for p in prow[r0:r0 + W]]
+                    if min(par) < 0 or max(par) >= W:
+                        raise RuntimeError(f"group {g}: a parent row outside the group ({prow[r0:r0 + W]})")
+                    r.cols.append(([int(t) for t in trow[r0:r0 + W]], par))
+                r.rounds += self.look
+                done = all(bool(f) for f in finished[r0:r0 + W])
+                if r.rounds >= r.max_new and not done:
+                    raise RuntimeError(f"group {g}: {r.rounds} rounds ran for a bound of {r.max_new} and the device says "
+                                       f"finished = {[int(f) for f in finished[r0:r0 + W]]}")
+                if not done:
+                    continue
+                k = min(r.rounds, r.max_new)   # the chunk ran on past the bound: those rounds are not the request's
+                hyps = beam_backtrack([c[0] for c in r.cols[:k]], [c[1] for c in r.cols[:k]],
+                                      [float(s) for s in scores[r0:r0 + W]], W, eos_id, length_penalty, num_return)[0]
+                self.live[g] = None
+                self._active.discard(r.id)
+                r.cols = []
+                retire = getattr(self.backend, "retire", None)
+                if retire is not None:
+                    retire(g, r)
+                yield r.id, hyps
+
+    def run(self, eos_id: int, length_penalty: float = 1.0, num_return: int = 1) -> dict:
+        return dict(self.drain(eos_id, length_penalty, num_return))
+
+
 def _u32_as_i32(x: int) -> int:
     return x - 2 ** 32 if x >= 2 ** 31 else x
 
@@ -1014,15 +1090,34 @@ class ContinuousGenerator:
     They are written behind every admission and extension that carries a rule (ergm_hist_write), a new tenant inherits
     nothing, a parked slot keeps its history, and while a ruled request is live every round bans before it samples and
     records what it drew (ergm_logit_rules_apply, ergm_hist_append: two launches more; ergm_decode_set_rules on the
-    executor engines).  While none is live the rounds launch what they always did."""
+    executor engines).  While none is live the rounds launch what they always did.
+
+    ``num_beams=W`` (1 .. 8, ``max_batch % W == 0``, not with ``controls``): beam mode.  The slots are ``max_batch // W``
+    groups, group g rows g·W .. g·W + W - 1, and a request is a beam search of W beams in one group: the admission
+    prefills its prompt into row g·W alone, ergm_beam_seed copies the caption K | V to the group's other rows and
+    leaves the scores [0, -inf, ...], and every round is ergm_beam_select, ergm_beam_gather and the slot step over all
+    rows (ergm_decode_run_slot_beams on the executor engines), so a group ends on the device at eos on every beam or at
+    its bound and is served again at the next look (``BeamScheduler``).  ``submit`` takes the logit rules per request,
+    ``run_beams`` / ``drain_beams`` / ``beam_search`` serve the queue, and the sampled entry points are refused."""
 
     ENGINES = BatchedGenerator.ENGINES
+    num_beams: Optional[int] = None   # beam mode: the beams per request, fixed for the generator's life
 
     def __init__(self, model, max_batch: int, max_len: int, cap_max: int, engine: str = "python",
                  max_admit: Optional[int] = None, max_admit_tokens: Optional[int] = None, keep_logits: bool = False,
-                 controls: bool = False, bad_words_cap: int = 64):
+                 controls: bool = False, bad_words_cap: int = 64, num_beams: Optional[int] = None):
         if engine not in self.ENGINES:
             raise ValueError(f"engine {engine!r} is not one of {sorted(self.ENGINES)}")
+        if num_beams is not None:
+            if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
+                raise ValueError(f"num_beams {num_beams!r} outside [1, 8]")
+            if max_batch < 1 or max_batch % num_beams:
+                raise ValueError(f"max_batch {max_batch} is no positive multiple of num_beams {num_beams}")
+            if num_beams > model.layout.vocab:
+                raise ValueError(f"num_beams {num_beams} > the vocabulary")
+            if controls:
+                raise ValueError("num_beams and controls=True do not go together: beam search draws nothing")
+        self.num_beams = num_beams
         if isinstance(bad_words_cap, bool) or not isinstance(bad_words_cap, int) or bad_words_cap < 1:
             raise ValueError(f"bad_words_cap {bad_words_cap!r} is not a positive integer")
         self.bad_words_cap = bad_words_cap
@@ -1034,7 +1129,11 @@ class ContinuousGenerator:
         self.max_batch, self.max_len, self.cap_max = max_batch, max_len, cap_max
         if max_admit_tokens is None:
             max_admit_tokens = min(2048, max_batch * max_len)
-        self.sched = SlotScheduler(self, max_batch, max_len, cap_max, max_admit, max_admit_tokens)
+        if num_beams is None:
+            self.sched = SlotScheduler(self, max_batch, max_len, cap_max, max_admit, max_admit_tokens)
+        else:   # the same policy over groups of num_beams slots
+            self.n_groups = max_batch // num_beams
+            self.sched = BeamScheduler(self, self.n_groups, num_beams, max_len, cap_max, max_admit, max_admit_tokens)
         self.keep_logits = keep_logits
         self.final_logits: dict = {}   # keep_logits: id -> the slot's logits row [V] when the request retired
         dev = self.dev = model.flat.device
@@ -1057,6 +1156,22 @@ class ContinuousGenerator:
         self._cap_host = [0] * mb   # the caption rows each slot was admitted with (extend's host check)
         self.controls = controls
         self.token_logprobs: dict = {}   # controls, logprobs=True: id -> one log-probability per token of the turn
+        if num_beams is not None:
+            self.beam_scores = torch.full((mb,), -math.inf, dtype=torch.float32, device=dev)
+            need = L.load().ergm_beam_select_workspace_size(mb, num_beams)
+            self._beam_ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+            self._beam_ids = (None, None)              # (eos_id, sp2_id) of the search in progress
+            self._grp_rows = [0] * self.n_groups       # host bound on the live lengths of each group (0: idle)
+            self.seed_calls = 0
+        if controls or num_beams is not None:
+            # logit rules: the slots' token histories, start | ngram per slot, and the bad-word pool
+            self.hist = torch.zeros(mb, max_len, dtype=torch.int32, device=dev)
+            self._rule_vals = torch.zeros(2, mb, dtype=torch.int32, device=dev)
+            self._bad_pool = torch.zeros(mb, bad_words_cap, dtype=torch.int32, device=dev)
+            self._rules = ops.rules_desc(self.hist, start=self._rule_vals[0], ngram=self._rule_vals[1], bad=self._bad_pool)
+            self._slot_ruled = [False] * mb    # the slot's device values hold a rule and its history is kept
+            self._rule_live = [False] * mb     # ... and a request is running in it
+            self._rules_bound = False          # the executor plan holds the rules (ergm_decode_set_rules)
         if controls:
             # rows: top_p, temperature, repetition penalty (f32 bits) and top_k, one column per slot
             self._ctl_vals = torch.zeros(4, mb, dtype=torch.int32, device=dev)
@@ -1068,14 +1183,6 @@ class ContinuousGenerator:
                                        min_step=self.min_step, seen=self.seen)
             self._slot_sp: List[Optional[SamplingParams]] = [None] * mb   # what each slot was last given
             self._lp_acc: List[Optional[list]] = [None] * mb              # the log-probabilities of the turn so far
-            # logit rules: the slots' token histories, start | ngram per slot, and the bad-word pool
-            self.hist = torch.zeros(mb, max_len, dtype=torch.int32, device=dev)
-            self._rule_vals = torch.zeros(2, mb, dtype=torch.int32, device=dev)
-            self._bad_pool = torch.zeros(mb, bad_words_cap, dtype=torch.int32, device=dev)
-            self._rules = ops.rules_desc(self.hist, start=self._rule_vals[0], ngram=self._rule_vals[1], bad=self._bad_pool)
-            self._slot_ruled = [False] * mb    # the slot's device values hold a rule and its history is kept
-            self._rule_live = [False] * mb     # ... and a request is running in it
-            self._rules_bound = False          # the executor plan holds the rules (ergm_decode_set_rules)
             self._hist_host: List[list] = [[] for _ in range(mb)]   # what each slot's cache holds, as segments
         if engine != "python":
             self._create_plan()
@@ -1533,6 +1640,7 @@ class ContinuousGenerator:
     def run_chunk(self, n: int):
         """n rounds of ergm_topp_sample_rows (``controls``: ergm_sample_rows) + one step over every slot; one read of
         the tokens and flags, and of the log-probabilities when a slot keeps them."""
+        self._no_beams("run_chunk")
         top_p, eos_id, sp2_id, seed = self._sampling
         B = self.max_batch
         out = torch.empty(n, B, dtype=torch.int64, device=self.dev)
@@ -1578,6 +1686,10 @@ class ContinuousGenerator:
         return both[:n * B].view(n, B).tolist(), both[n * B:n * B + B].tolist()
 
     def admit_requests(self, slots, requests) -> None:
+        if self.num_beams is not None:   # the scheduler's slots are groups
+            self.admit_beams(slots, [r.payload for r in requests], [r.max_new for r in requests], [r.id for r in requests],
+                             [r.sampling for r in requests])
+            return
         self.admit(slots, [r.payload for r in requests], [r.max_new for r in requests], [r.id for r in requests],
                    [r.sampling for r in requests] if self.controls else None)
 
@@ -1586,6 +1698,11 @@ class ContinuousGenerator:
                     [r.sampling for r in requests] if self.controls else None)
 
     def retire(self, slot: int, request) -> None:
+        if self.num_beams is not None:   # slot is the group: its rows hold no live length and no live rule any more
+            self._grp_rows[slot] = 0
+            for r in range(slot * self.num_beams, (slot + 1) * self.num_beams):
+                self._rule_live[r] = False
+            return
         if self.keep_logits:
             self.final_logits[request.id] = self.logits[slot].clone()
         if self.controls and self._lp_acc[slot] is not None:   # the chunk ran on past the request's last token
@@ -1601,7 +1718,7 @@ class ContinuousGenerator:
         """ValueError for what this generator cannot serve: any ``sampling`` without ``controls=True``, bad words that do
         not fit a pool row of ``bad_words_cap`` entries, a rule with a cache longer than the 1,024 positions the rule
         kernel stages.  The scheduler calls it at ``submit`` / ``extend``, the low-level ``admit`` / ``extend`` too."""
-        if sampling is not None and not self.controls:
+        if sampling is not None and not self.controls and getattr(self, "num_beams", None) is None:
             raise ValueError("sampling parameters need ContinuousGenerator(controls=True)")
         if sampling is not None and not isinstance(sampling, SamplingParams):
             raise ValueError("sampling must be a SamplingParams")
@@ -1611,10 +1728,29 @@ class ContinuousGenerator:
                 raise ValueError(f"logit rules need max_len <= 1024 (it is {self.max_len})")
 
     def submit(self, prompt, max_new_tokens: Optional[int] = None, request_id: Optional[int] = None,
-               keep: bool = False, sampling: Optional[SamplingParams] = None) -> int:
+               keep: bool = False, sampling: Optional[SamplingParams] = None, no_repeat_ngram_size: int = 0,
+               no_repeat_scope: str = "sequence", bad_words_ids=()) -> int:
         """Queue a prompt; returns its id (uint32; arrival order unless given).  ``keep``: the request keeps its slot
         and its cache when it ends (it is parked), so that ``extend_request`` can continue the conversation; a kept
-        prompt that carries visual / audio features has at least 2 tokens (the positions the features sit at)."""
+        prompt that carries visual / audio features has at least 2 tokens (the positions the features sit at).
+
+        Beam mode (``num_beams``): the request is served by ``run_beams`` / ``drain_beams`` in a group of ``num_beams``
+        slots; ``no_repeat_ngram_size`` / ``no_repeat_scope`` / ``bad_words_ids`` (``SamplingParams`` has their meaning)
+        are its logit rules, the same in all rows of its group.  ``keep`` and ``sampling`` are refused there, and the
+        three rule arguments outside it (a sampled request carries its rules in ``sampling``)."""
+        if self.num_beams is not None:
+            if keep or sampling is not None:
+                raise ValueError("beam mode has no sessions and draws nothing: keep / sampling are refused")
+            bad = check_rules(no_repeat_ngram_size, no_repeat_scope, bad_words_ids)
+            rules = None
+            if no_repeat_ngram_size > 0 or bad:
+                rules = SamplingParams(no_repeat_ngram_size=no_repeat_ngram_size, no_repeat_scope=no_repeat_scope,
+                                       bad_words_ids=bad)
+                self.check_sampling(rules)
+            return self.sched.submit(int(prompt[0].numel()), int(prompt[2].numel()), max_new_tokens, request_id, prompt,
+                                     False, sampling=rules)
+        if no_repeat_ngram_size or bad_words_ids or no_repeat_scope != "sequence":
+            raise ValueError("a sampled request carries its logit rules in sampling=SamplingParams(...)")
         if keep and prompt[3] is not None and int(prompt[0].numel()) < 2:
             raise ValueError("a kept prompt with visual / audio features needs at least 2 tokens")
         self.check_sampling(sampling)
@@ -1629,6 +1765,7 @@ class ContinuousGenerator:
         returned under the same id.  Raises ValueError when the id is not parked, the turn is empty or longer than
         max_admit_tokens, or the cache has no room for it and one new token.  ``sampling`` (``controls=True``): None
         keeps the session's values, except that the new turn has no minimum length."""
+        self._no_beams("extend_request")
         ids, token_types = ids.reshape(-1), token_types.reshape(-1)
         if ids.numel() != token_types.numel():
             raise ValueError("one token type per token")
@@ -1641,6 +1778,7 @@ class ContinuousGenerator:
 
     def drain(self, top_p: float, eos_id: int, sp2_id: int, seed: int = 0):
         """Serve the queue, yielding (id, tokens) as each request retires."""
+        self._no_beams("drain")
         self._sampling = (top_p, eos_id, sp2_id, seed)
         try:
             yield from self.sched.drain(eos_id)
@@ -1649,16 +1787,172 @@ class ContinuousGenerator:
 
     def run(self, top_p: float, eos_id: int, sp2_id: int, seed: int = 0) -> dict:
         """Serve the queue; returns {id: tokens}, each list ending at its first eos (included) or at its bound."""
+        self._no_beams("run")
         return dict(self.drain(top_p, eos_id, sp2_id, seed))
 
     def generate(self, prompts, top_p: float, eos_id: int, sp2_id: int, seed: int = 0, max_new_tokens=None,
                  sampling=None) -> List[List[int]]:
         """One token list per prompt, in submission order.  max_new_tokens: None, one bound for all, or one per prompt;
         sampling (``controls=True``): None, one ``SamplingParams`` for all, or one per prompt."""
+        self._no_beams("generate")
         if max_new_tokens is None or isinstance(max_new_tokens, int):
             max_new_tokens = [max_new_tokens] * len(prompts)
         if sampling is None or isinstance(sampling, SamplingParams):
             sampling = [sampling] * len(prompts)
         ids = [self.submit(p, k, sampling=sp) for p, k, sp in zip(prompts, max_new_tokens, sampling)]
         out = self.run(top_p, eos_id, sp2_id, seed)
+        return [out[i] for i in ids]
+
+    # ---- beam mode: beam search on the slots (num_beams) -----------------------------------------------------
+    def _no_beams(self, what: str) -> None:
+        if self.num_beams is not None:
+            raise ValueError(f"{what} samples: a generator in beam mode (num_beams={self.num_beams}) serves run_beams / "
+                             "drain_beams / beam_search")
+
+    def _need_beams(self, what: str) -> int:
+        if self.num_beams is None:
+            raise ValueError(f"{what} needs ContinuousGenerator(num_beams=W)")
+        return self.num_beams
+
+    def _set_beam_rules(self, groups, rules, ids_l, lens) -> None:
+        """The rule values of every row of the admitted groups (start, ngram, the bad-word pool row: one copy to the
+        device, two scatters) and the prompts of the ruled ones in the history of row g·W (one ergm_hist_write); round
+        0's ergm_hist_follow fans the history out.  An unruled group takes the values that ban nothing, so a new tenant
+        inherits no rule."""
+        W = self.num_beams
+        rows = []
+        for g, sp, n in zip(groups, rules, lens):
+            if sp is None:
+                vals = [0, 0] + [0] * self.bad_words_cap
+            else:
+                vals = [n if sp.no_repeat_scope == "turn" else 0, sp.no_repeat_ngram_size,
+                        *pack_bad_words(sp.bad_words_ids, self.bad_words_cap)]
+            rows += [[g * W + w] + vals for w in range(W)]
+        m = torch.tensor(rows, dtype=torch.int32).to(self.dev)
+        sl = m[:, 0].long()
+        self._rule_vals[:, sl] = m[:, 1:3].t()
+        self._bad_pool[sl] = m[:, 3:]
+        ruled = [b for b, sp in enumerate(rules) if sp is not None]
+        if ruled:
+            q0 = [sum(lens[i] for i in ruled[:j]) for j in range(len(ruled))]
+            w = torch.tensor([[groups[b] * W for b in ruled], q0, [lens[b] for b in ruled]], dtype=torch.int32).to(self.dev)
+            ids = torch.cat([ids_l[b] for b in ruled]).to(device=self.dev, dtype=torch.int64)
+            ops.hist_write(ids, w[0], w[1], w[2], self.hist, self.max_len)
+        for g, sp in zip(groups, rules):
+            for r in range(g * W, (g + 1) * W):
+                self._slot_ruled[r] = self._rule_live[r] = sp is not None
+
+    @torch.no_grad()
+    def admit_beams(self, groups, prompts, max_new_tokens=None, request_ids=None, rules=None) -> None:
+        """Prefill ``prompts`` into the free ``groups`` (low level; ``submit`` / ``run_beams`` do this through the
+        scheduler): the admission of prompt b into slot groups[b]·W alone, then ergm_beam_seed, which copies its caption
+        K | V to the group's other slots and leaves the scores [0, -inf, ...], the state round 0 starts from.
+        max_new_tokens: one bound per prompt (default: to the end of the cache); rules: one ``SamplingParams`` (its
+        three rule fields count) or None per prompt."""
+        W = self._need_beams("admit_beams")
+        groups = [int(g) for g in groups]
+        n_seq = len(prompts)
+        if len(groups) != n_seq or n_seq < 1:
+            raise ValueError("admit_beams takes one group per prompt")
+        if len(set(groups)) != n_seq or min(groups) < 0 or max(groups) >= self.n_groups:
+            raise ValueError(f"groups {groups}: outside [0, {self.n_groups}) or named twice")
+        rules = [None] * n_seq if rules is None else [sp if sp is not None and sp.has_rules else None for sp in rules]
+        if len(rules) != n_seq:
+            raise ValueError("one rules value per prompt")
+        for sp in rules:
+            self.check_sampling(sp)
+        ids_l = [p[0].reshape(-1) for p in prompts]
+        lens = [int(t.numel()) for t in ids_l]
+        self.admit([g * W for g in groups], prompts, max_new_tokens, request_ids)
+        if any(sp is not None for sp in rules) or any(self._slot_ruled[g * W] for g in groups):
+            self._set_beam_rules(groups, rules, ids_l, lens)
+        ops.beam_seed(self.xkv, groups, W, self.cap_max, self.lens, self.cap_lens, self.stop_lens, self.finished,
+                      self.beam_scores)
+        self.seed_calls += 1
+        for g, n in zip(groups, lens):
+            self._grp_rows[g] = n
+
+    def _beam_chunk(self, n: int, eos_id: Optional[int], sp2_id: Optional[int]):
+        """n rounds on the device; the tokens and parents [n, max_batch] stay there."""
+        W = self._need_beams("beam_round")
+        eos_id = self._beam_ids[0] if eos_id is None else eos_id
+        sp2_id = self._beam_ids[1] if sp2_id is None else sp2_id
+        if eos_id is None or sp2_id is None:
+            raise ValueError("beam_round needs eos_id and sp2_id")
+        V = self.m.layout.vocab
+        if not 0 <= eos_id < V:
+            raise ValueError(f"eos_id {eos_id} outside the vocabulary")
+        if n < 1:
+            raise ValueError(f"{n} round(s)")
+        self._beam_ids = (eos_id, sp2_id)
+        B, dev = self.max_batch, self.dev
+        toks = torch.empty(n, B, dtype=torch.int64, device=dev)
+        pars = torch.empty(n, B, dtype=torch.int32, device=dev)
+        ruled = any(self._rule_live)
+        bound = max(self._grp_rows)   # the host's bound on the live lengths
+        if self.engine != "python":
+            if ruled != self._rules_bound:
+                L.call("ergm_decode_set_rules", self._plan, C.byref(self._rules) if ruled else None)
+                self._rules_bound = ruled
+            p = lambda t: C.c_void_p(t.data_ptr())
+            L.call("ergm_decode_run_slot_beams", self._plan, n, W, bound, eos_id, sp2_id, p(self.beam_scores), p(toks), p(pars),
+                   p(self._beam_ws), self._beam_ws.numel(), self._stream())
+        else:
+            tt = torch.full((B,), sp2_id, dtype=torch.int64, device=dev)
+            for i in range(n):
+                if ruled:
+                    ops.logit_rules(self._logits, V, self._rules, self.lens, eos_id, self.max_len, finished=self.finished)
+                ops.beam_select(self._logits, V, W, self.beam_scores, self.finished, eos_id, parent=pars[i], token=toks[i],
+                                ws=self._beam_ws)
+                ops.beam_gather(self.kv, pars[i], self.lens, W, max_len=max(1, min(bound + i, self.max_len)))
+                if ruled:
+                    ops.hist_follow(self.hist, pars[i], self.lens, W, self.max_len)
+                    ops.hist_append(toks[i], self.lens, self.hist, self.max_len, finished=self.finished)
+                self.step(toks[i], tt)
+        self._grp_rows = [min(r + n, self.max_len) if r else 0 for r in self._grp_rows]
+        return toks, pars
+
+    @torch.no_grad()
+    def beam_round(self, n: int, eos_id: Optional[int] = None, sp2_id: Optional[int] = None):
+        """n rounds of select, gather, step over every slot (low level).  Returns ``(tokens, parents)``: n lists over
+        the max_batch rows, read back once; the scores and flags stay on the device (``beam_scores``, ``finished``)."""
+        toks, pars = self._beam_chunk(n, eos_id, sp2_id)
+        return toks.cpu().tolist(), pars.cpu().tolist()
+
+    @torch.no_grad()
+    def run_beam_chunk(self, n: int):
+        """The scheduler's chunk: n rounds, then one read of the tokens, parents, flags and scores."""
+        toks, pars = self._beam_chunk(n, None, None)
+        B = self.max_batch
+        both = torch.cat([toks.reshape(-1), pars.reshape(-1).to(torch.int64), self.finished.to(torch.int64),
+                          self.beam_scores.view(torch.int32).to(torch.int64)]).cpu()
+        scores = both[2 * n * B + B:].to(torch.int32).view(torch.float32).tolist()
+        return (both[:n * B].view(n, B).tolist(), both[n * B:2 * n * B].view(n, B).tolist(),
+                both[2 * n * B:2 * n * B + B].tolist(), scores)
+
+    def drain_beams(self, eos_id: int, sp2_id: int, length_penalty: float = 1.0, num_return: int = 1):
+        """Serve the queue by beam search, yielding (id, [(tokens, sum_logprob), ...]) as each group retires."""
+        self._need_beams("drain_beams")
+        if not 0 <= eos_id < self.m.layout.vocab:
+            raise ValueError(f"eos_id {eos_id} outside the vocabulary")
+        self._beam_ids = (eos_id, sp2_id)
+        return self.sched.drain(eos_id, length_penalty, num_return)
+
+    def run_beams(self, eos_id: int, sp2_id: int, length_penalty: float = 1.0, num_return: int = 1) -> dict:
+        """Serve the queue by beam search; returns {id: [(tokens, sum_logprob), ...]}: ``num_return`` hypotheses per
+        request, best first by ``sum_logprob / len(tokens) ** length_penalty`` (``beam_backtrack``), each ending at its
+        first eos (included) or at the request's ``max_new_tokens``.  The device ranks by the raw sum."""
+        return dict(self.drain_beams(eos_id, sp2_id, length_penalty, num_return))
+
+    def beam_search(self, prompts, eos_id: int, sp2_id: int, max_new_tokens=None, length_penalty: float = 1.0,
+                    num_return: int = 1, no_repeat_ngram_size: int = 0, no_repeat_scope: str = "sequence",
+                    bad_words_ids=()) -> list:
+        """One hypothesis list per prompt, in submission order.  max_new_tokens: None, one bound for all, or one per
+        prompt; the rule arguments hold for every prompt."""
+        self._need_beams("beam_search")
+        if max_new_tokens is None or isinstance(max_new_tokens, int):
+            max_new_tokens = [max_new_tokens] * len(prompts)
+        ids = [self.submit(p, k, no_repeat_ngram_size=no_repeat_ngram_size, no_repeat_scope=no_repeat_scope,
+                           bad_words_ids=bad_words_ids) for p, k in zip(prompts, max_new_tokens)]
+        out = self.run_beams(eos_id, sp2_id, length_penalty, num_return)
         return [out[i] for i in ids]

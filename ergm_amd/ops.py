@@ -662,6 +662,36 @@ def beam_gather(caches, parent, lens, W: int, max_len: Optional[int] = None):
            _ptr(lens), R, W, rows, _stream(c0.device))
 
 
+def beam_seed(xkv, groups, W: int, cap_max: int, lens, cap_lens, stop_lens, finished, scores, groups_dev=None):
+    """Seed groups of W slots behind an admission that filled row g·W of each (ergm_beam_seed): ``xkv`` is a list of
+    per-layer caption caches [max_batch, rows >= cap_max, width] with the same strides; for every g in ``groups`` (host
+    ints) the caption rows [0, clamp(cap_lens[g·W], 0, cap_max)) of every layer go from slot g·W to the group's other
+    slots, those rows get that caption length, stop_lens[g·W], lens 0, finished 0 and score -inf, and scores[g·W] = 0.
+    ``groups_dev``: the same ids as int32 on the device (default: copied from ``groups``)."""
+    _need_gpu(lens, cap_lens, stop_lens, finished, scores, *xkv)
+    c0 = xkv[0]
+    for c in xkv:
+        assert c.dim() == 3 and c.dtype == c0.dtype and c.shape == c0.shape and c.stride() == c0.stride() and c.stride(2) == 1
+    for t in (lens, cap_lens, stop_lens):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert finished.dtype == torch.uint8 and scores.dtype == torch.float32 and finished.is_contiguous() and scores.is_contiguous()
+    mb = c0.shape[0]
+    if min(t.numel() for t in (lens, cap_lens, stop_lens, finished, scores)) < mb:
+        raise ValueError("beam_seed: fewer state rows than cache slots")
+    if not 1 <= cap_max <= c0.shape[1]:
+        raise ValueError(f"beam_seed: cap_max {cap_max} outside [1, {c0.shape[1]}]")
+    groups = [int(g) for g in groups]
+    if groups_dev is None:
+        groups_dev = torch.tensor(groups, dtype=torch.int32).to(c0.device)
+    assert groups_dev.dtype == torch.int32 and groups_dev.is_contiguous() and groups_dev.numel() == len(groups)
+    _need_gpu(groups_dev)
+    es = c0.element_size()
+    ptrs = (C.c_void_p * len(xkv))(*[c.data_ptr() for c in xkv])
+    L.call("ergm_beam_seed", ptrs, len(xkv), c0.stride(0) * es, c0.stride(1) * es, c0.shape[2] * es, _ptr(groups_dev),
+           (C.c_int * len(groups))(*groups), len(groups), W, mb, cap_max, _ptr(lens), _ptr(cap_lens), _ptr(stop_lens),
+           _ptr(finished), _ptr(scores), _stream(c0.device))
+
+
 def rules_desc(hist, start=None, ngram=None, bad=None) -> L.LogitRules:
     """ergm_logit_rules over device tensors: hist int32 [R, >= max_len] (rows ld_hist apart), start / ngram int32 [R],
     bad int32 [R, ld_bad] (length-prefixed sequences); None turns a rule off.  The struct holds addresses only: the

@@ -108,7 +108,8 @@ class Trainer:
     @torch.no_grad()
     def test(self, loader, top_p: float, eos_id: int, sp2_id: int, seed: int = 0, max_batch: int = 8,
              max_len: Optional[int] = None, engine: str = "python", sampling=None, num_beams: Optional[int] = None,
-             no_repeat_ngram_size: int = 0, no_repeat_scope: str = "sequence", bad_words_ids=()):
+             no_repeat_ngram_size: int = 0, no_repeat_scope: str = "sequence", bad_words_ids=(),
+             beam_batching: str = "static"):
         """The reference's ``test()`` (src/main.py:291-335) without the tokenizer: one sampled response for every
         sample of ``loader``, all of them served by one ``ContinuousGenerator`` of ``max_batch`` slots.  A sample's
         prompt is its first n tokens, n = the count of tokens that are not ``eos_id`` (the collate pads with eos), with
@@ -120,8 +121,14 @@ class Trainer:
         beams instead of a sample (``BatchedGenerator.beam_search`` in static batches of ``max_batch // W`` prompts;
         ``top_p``, ``seed`` and ``sampling`` are not used); None is the sampled path, unchanged.
         ``no_repeat_ngram_size`` / ``no_repeat_scope`` / ``bad_words_ids`` go to the beam search (the sampled path
-        carries them in ``sampling``)."""
+        carries them in ``sampling``).  ``beam_batching``: "static" (default) is that path; "continuous" serves the
+        loader through one beam-mode ``ContinuousGenerator`` of ``max_batch // W`` groups, every sample with its own
+        bound ``max_len`` - its prompt."""
         from .generate import BatchedGenerator, ContinuousGenerator
+        if beam_batching not in ("static", "continuous"):
+            raise ValueError(f"beam_batching {beam_batching!r} is not \"static\" or \"continuous\"")
+        if beam_batching != "static" and num_beams is None:
+            raise ValueError("beam_batching needs num_beams")
         self.model.eval()
         dev = self.device
         prompts, refs, emos, losses = [], [], [], []
@@ -149,6 +156,13 @@ class Trainer:
             per = max_batch // num_beams if num_beams >= 1 else 0
             if per < 1:
                 raise ValueError(f"num_beams {num_beams} outside [1, max_batch {max_batch}]")
+            if beam_batching == "continuous":
+                gen = ContinuousGenerator(self.model, max_batch=per * num_beams, max_len=max_len,
+                                          cap_max=max(int(p[2].numel()) for p in prompts), engine=engine,
+                                          num_beams=num_beams)
+                out = gen.beam_search(prompts, eos_id, sp2_id, no_repeat_ngram_size=no_repeat_ngram_size,
+                                      no_repeat_scope=no_repeat_scope, bad_words_ids=bad_words_ids)
+                return [h[0][0] for h in out], refs, emos, [float(x) for x in torch.stack(losses).tolist()]
             beams = BatchedGenerator(self.model, max_batch=max_batch, max_len=max_len, engine=engine)
             hyps = []
             for i in range(0, len(prompts), per):

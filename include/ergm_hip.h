@@ -918,6 +918,43 @@ int ergm_beam_gather(void* const* caches, int n_layer, int64_t ld_seq, int64_t l
 int ergm_decode_run_beams(ergm_decode_plan* plan, int n, int W, int64_t eos_id, int64_t sp2_id, float* scores,
                           int64_t* tokens_out, int* parents_out, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- Beam search in slot mode (found by symbol, ABI unchanged) -----------------------------------------------------
+ * The max_batch slots of ergm_decode_bind_slots are G = max_batch / W groups of W slots, group g rows g·W .. g·W + W - 1:
+ * the layout select and gather assume.  A prompt enters a group through ergm_decode_admit with slots[b] = g_b·W, which
+ * fills row g·W alone; ergm_beam_seed, on the same stream behind it, leaves the group in the state round 0 starts from:
+ *   - rows [0, c) of every layer's caption K | V go from slot g·W to slots g·W + 1 .. g·W + W - 1, with
+ *     c = clamp(cap_lens[g·W], 0, cap_max) read on the device and clamped before an address is formed (slot s of layer
+ *     l at xkv[l] + s·ld_seq, its row i at + i·ld_row, row_bytes each; bytes, multiples of 16; the gather's layout: a
+ *     workgroup per (destination row, layer, 64-row chunk), a wave per row, up to 48 layers per launch);
+ *   - rows g·W + w, w >= 1: cap_lens = c, stop_lens = stop_lens[g·W], lens = 0, finished = 0, scores = -inf;
+ *   - row g·W: scores = 0, and nothing else of it is written.
+ * The kernels read the group ids from groups_dev (device int32 [n_grp]); an id outside [0, G) writes nothing.  Every
+ * destination row has one writer and what is read (cap_lens / stop_lens of row g·W, its caption rows) is written by
+ * nobody, so the launches need no ordering among themselves: plain stores, no atomics.  groups is the same list on the
+ * host.  ERGM_EINVAL before any launch for an id outside [0, G) or named twice, n_grp outside [1, G], W outside [1, 8],
+ * max_batch % W != 0, strides or row_bytes that are no multiples of 16, and a null pointer.  W = 1 launches the state
+ * kernel only.
+ *
+ * ergm_decode_run_slot_beams: n rounds over all max_batch slots of a plan bound in slot mode.  A round is
+ * ergm_logit_rules_apply while ergm_decode_set_rules holds rules, ergm_beam_select with R = max_batch on the bound
+ * logits and finished flags into tokens_out[i] / parents_out[i] (device int64 / int32 [n][max_batch]) and scores
+ * (device f32 [max_batch]), ergm_beam_gather over the bound self-attention caches and lens, ergm_hist_follow +
+ * ergm_hist_append under rules, then ergm_decode_step_slots' kernels on the round's tokens typed sp2_id: a live row
+ * advances and is finished by the device when its length reaches stop_lens, so a group ends at eos on every beam or at
+ * its bound.  An idle or finished group offers eos at unchanged scores and moves nothing.  rows_bound is the caller's
+ * host bound on the live lengths at entry: the gather's grid covers min(rows_bound + i, max_len) cache rows in round i;
+ * the kernel's own clamp keeps a wrong bound from reading or writing outside a cache, but rows past it are not copied,
+ * so the caller passes a correct one.  One stream, no events, nothing read back.  workspace: that of ergm_beam_select
+ * for (max_batch, W).  ERGM_EINVAL before any launch for a plan not bound in slot mode, n < 1, W outside [1, 8] or above
+ * the vocabulary, max_batch % W != 0, eos_id outside the vocabulary, rows_bound outside [0, max_len], a null or
+ * misaligned argument, and a workspace below ergm_beam_select_workspace_size(max_batch, W).                            */
+int ergm_beam_seed(void* const* xkv, int n_layer, int64_t ld_seq, int64_t ld_row, int row_bytes, const int* groups_dev,
+                   const int* groups, int n_grp, int W, int max_batch, int cap_max, int* lens, int* cap_lens, int* stop_lens,
+                   uint8_t* finished, float* scores, void* stream);
+int ergm_decode_run_slot_beams(ergm_decode_plan* plan, int n, int W, int rows_bound, int64_t eos_id, int64_t sp2_id,
+                               float* scores, int64_t* tokens_out, int* parents_out, void* workspace, size_t ws_bytes,
+                               void* stream);
+
 /* ---- Logit rules: no repeated n-gram, bad words (found by symbol, ABI unchanged) ------------------------------------
  * Both rules need the ordered tokens of a row, which no other kernel keeps: hist is int32 [R][ld_hist], row r holding
  * the prompt and the generated tokens of the sequence in row r at their sequence positions.  For a row r:

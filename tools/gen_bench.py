@@ -50,6 +50,10 @@ everything under it are the parent commit's code, which the feature does not tou
 per round, and the launches of a round alone in back-to-back windows of 200, alternating: select, the sampler launch
 (ergm_topp_sample_rows), the gather of round 0 (W - 1 of W rows move) and a gather in which every beam keeps its row.
 The whole runs in fresh child processes with ERGM_BEAM_SELECT=two and =one, alternating twice.
+Beam search on the slots, ``--beams W --requests [--engines python,native,fused]``: the 256 requests by
+beam search, per engine, as static arrival-order batches of 32 // W prompts (BatchedGenerator.beam_search, each batch to
+its largest bound) and through one beam-mode ContinuousGenerator of 32 slots, alternating in one process, median of 5
+after a warm-up: requested tokens/s, rounds and rounds per requested token of both, and the seed launch alone.
 Without --case the tool runs every case in turn, each in a fresh child process under its own timeout, one at a
 time, and stops at the first that fails.  --cases a,b,c runs those cases in that
 order (e.g. b32,n32,f32,b32,n32,f32 to alternate engines on one box).  For the kernel-time split of one engine:
@@ -117,6 +121,14 @@ def _generation(case):
                       "ms_all": [round(x, 2) for x in ms], "tokens_per_s": round(B * NEW / med * 1e3, 1)}), flush=True)
 
 
+def request_lengths(n):
+    """The seeded max_new_tokens of the n requests: min(NEW, 2 + a geometric variable of mean 15).  Host only."""
+    import torch
+    geo = torch.distributions.Geometric(probs=torch.tensor(1.0 / REQ_MEAN))   # failures before a success: mean 15
+    torch.manual_seed(2)
+    return [min(NEW, 2 + int(geo.sample())) for _ in range(n)]                # 1 + a geometric variable of mean 16
+
+
 def _setup_requests(n):
     import torch
     from ergm_amd.config import ERGMConfig, NO_DROPOUT
@@ -127,10 +139,7 @@ def _setup_requests(n):
     g = torch.Generator().manual_seed(1)
     prompts = [(torch.randint(0, 50000, (1, PROMPT), generator=g).to(dev), torch.full((1, PROMPT), SP2, device=dev),
                 torch.randint(0, 50000, (1, CAPS), generator=g).to(dev), None, None) for _ in range(n)]
-    geo = torch.distributions.Geometric(probs=torch.tensor(1.0 / REQ_MEAN))   # failures before a success: mean 15
-    torch.manual_seed(2)
-    new = [min(NEW, 2 + int(geo.sample())) for _ in range(n)]                 # 1 + a geometric variable of mean 16
-    return dev, model, prompts, new
+    return dev, model, prompts, request_lengths(n)
 
 
 def _requests(case):
@@ -413,6 +422,72 @@ def _beams(W):
                           **({"bytes": fan_bytes, "cache_rows": int(lens[0])} if n == "gather_fan_out" else {})}), flush=True)
 
 
+def _beam_requests(W):
+    """--beams W --requests: the 256-request list by beam search, per engine, served two ways that alternate in one
+    process: static (BatchedGenerator.beam_search in arrival-order batches of 32 // W prompts, each with its largest
+    bound: the static path of Trainer.test) and continuous (a beam-mode ContinuousGenerator of 32 slots).  Then the seed
+    launch alone, for one group and for all of them."""
+    import torch
+    from ergm_amd import ops
+    from ergm_amd.generate import BatchedGenerator, ContinuousGenerator
+    R = 32
+    G = R // W
+    dev, model, prompts, new = _setup_requests(N_REQ)
+    only = sys.argv[sys.argv.index("--engines") + 1].split(",") if "--engines" in sys.argv else list(ENGINES.values())
+    for engine in only:
+        gen_s = BatchedGenerator(model, max_batch=R, max_len=PROMPT + NEW, engine=engine)
+        gen_c = ContinuousGenerator(model, max_batch=R, max_len=PROMPT + NEW, cap_max=CAPS, engine=engine, num_beams=W)
+        rounds = {"static": 0, "continuous": 0}
+        calls = {"admit": 0, "seed": 0}
+
+        def static():
+            rounds["static"] = 0
+            for i in range(0, N_REQ, G):
+                k = max(new[i:i + G])
+                out = gen_s.beam_search(prompts[i:i + G], W, BEAM_EOS, SP2, max_new_tokens=k)
+                assert all(len(h[0][0]) == k for h in out)
+                rounds["static"] += k
+
+        def continuous():
+            s0, a0, d0 = gen_c.sched.steps, gen_c.admit_calls, gen_c.seed_calls
+            out = gen_c.beam_search(prompts, BEAM_EOS, SP2, max_new_tokens=new)
+            assert [len(h[0][0]) for h in out] == new
+            rounds["continuous"] = gen_c.sched.steps - s0
+            calls["admit"], calls["seed"] = gen_c.admit_calls - a0, gen_c.seed_calls - d0
+        ms = {"static": [], "continuous": []}
+        for rep in range(REPEATS + 1):   # alternating; the first of each is the warm-up
+            for name, fn in (("static", static), ("continuous", continuous)):
+                t = _event_ms(fn)
+                if rep:
+                    ms[name].append(t)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        print(json.dumps({"case": "beam_requests", "engine": engine, "W": W, "groups": G, "requests": N_REQ,
+                          "requested_tokens": sum(new),
+                          **{f"{k}_ms_median": round(med[k], 2) for k in ms}, **{f"{k}_ms_all": [round(x, 2) for x in ms[k]] for k in ms},
+                          **{f"{k}_tokens_per_s": round(sum(new) / med[k] * 1e3, 1) for k in ms},
+                          **{f"{k}_rounds": rounds[k] for k in ms},
+                          **{f"{k}_rounds_per_token": round(rounds[k] / sum(new), 4) for k in ms},
+                          "admit_calls": calls["admit"], "seed_calls": calls["seed"],
+                          "speedup": round(med["static"] / med["continuous"], 3)}), flush=True)
+    # the seed launch alone, behind an admission of every group
+    gen = ContinuousGenerator(model, max_batch=R, max_len=PROMPT + NEW, cap_max=CAPS, engine="native", num_beams=W)
+    gen.admit_beams(list(range(G)), prompts[:G])
+    N = 200
+    for groups in ([0], list(range(G))):
+        gdev = torch.tensor(groups, dtype=torch.int32, device=dev)
+
+        def seed():
+            for _ in range(N):
+                ops.beam_seed(gen.xkv, groups, W, CAPS, gen.lens, gen.cap_lens, gen.stop_lens, gen.finished, gen.beam_scores,
+                              groups_dev=gdev)
+        seed()
+        us = [_event_ms(seed) / N * 1e3 for _ in range(REPEATS)]
+        kv_row = 2 * model.config.n_embd * 2
+        print(json.dumps({"case": "beam_requests", "launch": "seed", "W": W, "groups": len(groups),
+                          "bytes": len(groups) * (W - 1) * CAPS * kv_row * model.config.n_layer,
+                          "us_per_call": round(statistics.median(us), 2), "us_all": [round(x, 2) for x in us]}), flush=True)
+
+
 def _attention():
     import torch
     from ergm_amd import ops
@@ -447,6 +522,8 @@ def main():
         W = int(sys.argv[sys.argv.index("--beams") + 1])
         if not 1 <= W <= 8 or 32 % W:
             raise SystemExit("--beams takes 1, 2, 4 or 8")
+        if "--requests" in sys.argv:   # one process: the two ways alternate inside it
+            return _beam_requests(W)
         if "--child" in sys.argv:
             return _beams(W)
         for mode in ("two", "one", "two", "one"):   # the two forms of select, alternating, a fresh process each
