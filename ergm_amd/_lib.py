@@ -95,7 +95,25 @@ class LogitRules(C.Structure):
                 ("bad", C.c_void_p), ("ld_bad", C.c_int)]
 
 
+class SessionHdr(C.Structure):
+    """ergm_session_hdr (ergm_hip.h): the 64-byte header of a session blob, as the host keeps it."""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("flags", C.c_uint32), ("n_layer", C.c_int32),
+                ("row_bytes", C.c_int32), ("rows", C.c_int32), ("cap_rows", C.c_int32), ("row_id", C.c_uint32),
+                ("row_steps", C.c_uint32), ("ld_seen", C.c_int32), ("bad_cap", C.c_int32), ("reserved0", C.c_int32),
+                ("bytes", C.c_uint64), ("reserved1", C.c_uint32 * 2)]
+
+
+class SessionState(C.Structure):
+    """ergm_session_state (ergm_hip.h): the bound buffers a save or a load works on."""
+    _fields_ = [("kv", C.POINTER(C.c_void_p)), ("xkv", C.POINTER(C.c_void_p)), ("n_layer", C.c_int), ("row_bytes", C.c_int),
+                ("kv_ld_seq", C.c_int64), ("kv_ld_row", C.c_int64), ("xkv_ld_seq", C.c_int64), ("xkv_ld_row", C.c_int64),
+                ("max_batch", C.c_int), ("max_len", C.c_int), ("cap_max", C.c_int), ("lens", C.c_void_p),
+                ("cap_lens", C.c_void_p), ("stop_lens", C.c_void_p), ("finished", C.c_void_p), ("row_ids", C.c_void_p),
+                ("row_steps", C.c_void_p), ("ctl", C.POINTER(SampleCtl)), ("rules", C.POINTER(LogitRules))]
+
+
 NGRAM_MAX = 8  # ERGM_NGRAM_MAX
+SESSION_CTL, SESSION_RULES, SESSION_META_ROWS, SESSION_MAGIC = 1, 2, 6, 0x53475245  # ERGM_SESSION_*
 vp, i32, i64, f32, f64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 _SIGS = {
     "ergm_version": (i32, []),
@@ -166,6 +184,13 @@ _SIGS = {
     "ergm_hist_append": (i32, [vp, vp, vp, i32, vp, i32, i32, vp]),
     "ergm_hist_follow": (i32, [vp, i32, vp, vp, i32, i32, i32, vp]),
     "ergm_decode_set_rules": (i32, [vp, C.POINTER(LogitRules)]),
+    "ergm_session_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32]),
+    "ergm_session_header": (i32, [i32, i32, i32, i32, i32, i32, i32, C.POINTER(SessionHdr)]),
+    "ergm_session_launches": (i32, [i32]),
+    "ergm_slots_save": (i32, [C.POINTER(SessionState), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
+                              C.POINTER(vp), C.POINTER(sz), vp, vp]),
+    "ergm_slots_load": (i32, [C.POINTER(SessionState), i32, C.POINTER(i32), C.POINTER(SessionHdr), C.POINTER(vp),
+                              C.POINTER(sz), vp, vp, vp]),
     "ergm_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "ergm_layernorm_bwd_workspace_size": (sz, [i32, i32]),
     "ergm_layernorm_bwd": (i32, [vp] * 10 + [sz, i32, i32, vp, vp]),

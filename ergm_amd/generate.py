@@ -729,7 +729,7 @@ class SamplingParams:
 
 
 class _Request:
-    __slots__ = ("id", "n", "c", "max_new", "payload", "tokens", "slot", "keep", "past", "sampling", "rounds", "cols")
+    __slots__ = ("id", "n", "c", "max_new", "payload", "tokens", "slot", "keep", "past", "sampling", "rounds", "cols", "share")
 
     def __init__(self, rid: int, n: int, c: int, max_new: int, payload, keep: bool = False, past: int = 0, sampling=None):
         self.id, self.n, self.c, self.max_new, self.payload = rid, n, c, max_new, payload
@@ -737,6 +737,7 @@ class _Request:
         self.rounds = 0            # beam mode: the rounds run since the admission
         self.cols: List[tuple] = []   # beam mode: per round, the group's (tokens, parents within the group)
         self.slot = NO_REQUEST
+        self.share = None     # a continuation of a stored session: the byte count its blob is accounted under
         self.keep = keep      # park the slot when the request ends
         self.past = past      # a continuation: the rows its slot already holds (n counts the new ones)
         self.sampling = sampling   # a SamplingParams or None, for the backend
@@ -770,12 +771,46 @@ class SlotScheduler:
     ``extend_requests`` call per group, and the admissions into free slots follow.  The new turn's tokens are returned
     under the same id.  ``release`` frees a parked slot.  A parked slot is stepped like any finished slot: the step's
     append lands in the row behind its length, which the next extension overwrites before it reads it.  A slot parked
-    with its cache full (length ``max_len``) has no room and cannot be continued, only released."""
+    with its cache full (length ``max_len``) has no room and cannot be continued, only released.
+
+    ``store=True``: the session store.  A parked session may leave its slot: it is then *stored* (``stored``: id ->
+    (rows, caption rows)), which frees the slot, and returns into any free slot when its next turn arrives.  The backend
+    adds ``save_sessions(slots, ids)`` (pack the parked sessions of these slots away under their ids; the ids are still
+    in ``parked`` during the call), ``load_sessions(slots, ids)`` (unpack stored sessions into free slots, parked),
+    ``drop_session(id)`` (forget a stored session), ``fork_session(id, new_id)`` (a second stored session with the same
+    contents) and, optionally, ``session_bytes(slot, rows, c)`` (what a parked session costs, for ``store_bytes``).  At each look,
+    before the continuations and the admissions:
+
+    1. ``want`` = the waiting continuations of stored sessions + the queued requests; when that exceeds the free slots,
+       ``min(want - free, evictable)`` parked sessions are evicted, the least recently parked first (ties by slot), in
+       one ``save_sessions`` call.  A session whose continuation waits is not in ``parked`` and is never evicted; one
+       that would take the stored bytes above ``store_bytes`` is passed over.
+    2. The stored sessions with a waiting continuation take free slots in arrival order, the slot chosen as an
+       admission's is, in one ``load_sessions`` call; those that find no slot keep their place and go first next time.
+    3. The continuations and the admissions follow as without a store.
+
+    ``extend`` and ``release`` take stored ids as they take parked ones; ``offload`` stores a parked session at once;
+    ``fork`` gives a second id the same history (both share one stored copy, which is never written again).  Without a
+    byte cap the all-parked deadlock cannot occur; with one that blocks the eviction it is raised as before.  With
+    ``store=False`` nothing changes."""
 
     def __init__(self, backend, max_batch: int, max_len: int, cap_max: int, max_admit: Optional[int] = None,
-                 max_admit_tokens: Optional[int] = None, look: int = 8):
+                 max_admit_tokens: Optional[int] = None, look: int = 8, store: bool = False,
+                 store_bytes: Optional[int] = None):
         if max_batch < 1 or max_len < 2 or cap_max < 1 or look < 1:
             raise ValueError("max_batch, cap_max, look must be at least 1 and max_len at least 2")
+        if store_bytes is not None and (not store or isinstance(store_bytes, bool) or not isinstance(store_bytes, int)
+                                        or store_bytes < 0):
+            raise ValueError(f"store_bytes {store_bytes!r} needs store=True and a non-negative integer")
+        self.store, self.store_bytes = bool(store), store_bytes
+        self.stored: dict = {}                # id -> (rows in its blob, caption rows)
+        self.stored_waiting: List[_Request] = []   # continuations of stored sessions waiting for a slot, arrival order
+        self.stored_bytes = 0                 # what the stored sessions cost (a fork shares its origin's blob)
+        self._share: dict = {}                # stored id -> [bytes, ids sharing the blob]
+        self._parked_at: dict = {}            # parked id -> the look it was parked at
+        self._looks = 0
+        self.saves: List[List[tuple]] = []    # per save_sessions call: (session id, slot) pairs
+        self.loads: List[List[tuple]] = []    # per load_sessions call: (session id, slot) pairs
         self.backend, self.max_batch, self.max_len, self.cap_max, self.look = backend, max_batch, max_len, cap_max, look
         self.max_admit = max_batch if max_admit is None else max_admit
         self.max_admit_tokens = max_batch * max_len if max_admit_tokens is None else max_admit_tokens
@@ -832,11 +867,12 @@ class SlotScheduler:
         not parked, n_new is outside [1, max_admit_tokens], or the cache has no room for the new rows and one new
         token; also when the slot holds fewer than 2 rows (a one-token prompt that drew eos at once: the first two
         positions belong to the admission)."""
-        if request_id not in self.parked:
-            raise ValueError(f"request id {request_id} is not parked")
+        if request_id not in self.parked and request_id not in self.stored:
+            raise ValueError(f"request id {request_id} is not parked" + (" or stored" if self.store else ""))
         if getattr(self.backend, "extend_requests", None) is None:
             raise ValueError("the backend cannot extend a request (no extend_requests)")
-        slot, length, c = self.parked[request_id]
+        is_stored = request_id in self.stored
+        slot, length, c = (NO_REQUEST, *self.stored[request_id]) if is_stored else self.parked[request_id]
         if not 1 <= n_new <= self.max_admit_tokens:
             raise ValueError(f"{n_new} new tokens outside [1, max_admit_tokens {self.max_admit_tokens}]")
         room = self.max_len - length - n_new
@@ -852,9 +888,15 @@ class SlotScheduler:
         if sampling is not None:
             sampling.check_bound(max_new_tokens)
             self._backend_check(sampling)
-        del self.parked[request_id]
         r = _Request(request_id, n_new, c, max_new_tokens, payload, keep, past=length, sampling=sampling)
         r.slot = slot
+        if is_stored:   # it waits for a slot first: the next look loads it
+            del self.stored[request_id]
+            r.share = self._share.pop(request_id)
+            self.stored_waiting.append(r)
+            return request_id
+        del self.parked[request_id]
+        self._parked_at.pop(request_id, None)
         self.continuations.append(r)
         return request_id
 
@@ -865,12 +907,120 @@ class SlotScheduler:
             check(sampling)
 
     def release(self, request_id: int) -> None:
-        """Free the slot of a parked request."""
+        """Free the slot of a parked request, or forget a stored one."""
+        if request_id in self.stored:
+            del self.stored[request_id]
+            self._unshare(request_id, self._share.pop(request_id))
+            self.backend.drop_session(request_id)
+            self._active.discard(request_id)
+            return
         if request_id not in self.parked:
-            raise ValueError(f"request id {request_id} is not parked")
+            raise ValueError(f"request id {request_id} is not parked" + (" or stored" if self.store else ""))
         slot, _, _ = self.parked.pop(request_id)
+        self._parked_at.pop(request_id, None)
         self._held.discard(slot)
         self._active.discard(request_id)
+
+    # ---- the session store ----------------------------------------------------------------------------------
+    def _need_store(self, what: str) -> None:
+        if not self.store:
+            raise ValueError(f"{what} needs the session store (store=True)")
+
+    def _session_bytes(self, slot: int, rows: int, c: int) -> int:
+        size = getattr(self.backend, "session_bytes", None)
+        return 0 if size is None else int(size(slot, rows, c))
+
+    def _unshare(self, request_id: int, share: list) -> None:
+        """``request_id`` no longer uses the blob ``share`` accounts for; the last user's leaving frees its bytes."""
+        share[1].discard(request_id)
+        if not share[1]:
+            self.stored_bytes -= share[0]
+
+    def _save(self, ids: List[int]) -> None:
+        """The parked sessions ``ids`` leave their slots in one ``save_sessions`` call."""
+        slots = [self.parked[i][0] for i in ids]
+        nbytes = [self._session_bytes(*self.parked[i]) for i in ids]
+        self.backend.save_sessions(slots, ids)
+        for i, b in zip(ids, nbytes):
+            slot, rows, c = self.parked.pop(i)
+            self._parked_at.pop(i, None)
+            self._held.discard(slot)
+            self.stored[i] = (rows, c)
+            self._share[i] = [b, {i}]
+            self.stored_bytes += b
+        self.saves.append(list(zip(ids, slots)))
+
+    def _fits(self, nbytes: int) -> bool:
+        return self.store_bytes is None or self.stored_bytes + nbytes <= self.store_bytes
+
+    def offload(self, request_id: int) -> None:
+        """Store a parked session at once, which frees its slot; a stored id is left as it is.  Raises ValueError for an
+        id that is neither parked nor stored (a waiting continuation included) and when ``store_bytes`` has no room."""
+        self._need_store("offload")
+        if request_id in self.stored:
+            return
+        if request_id not in self.parked:
+            raise ValueError(f"request id {request_id} is not parked or stored")
+        if not self._fits(self._session_bytes(*self.parked[request_id])):
+            raise ValueError(f"request id {request_id}: store_bytes {self.store_bytes} has no room for the session")
+        self._save([request_id])
+
+    def fork(self, request_id: int, new_id: Optional[int] = None) -> int:
+        """A second session with the history of ``request_id`` under ``new_id`` (default: the next id), stored; a parked
+        origin is offloaded first.  Both share one stored copy.  Raises ValueError for an id that is neither parked nor
+        stored (a waiting continuation included) and for a ``new_id`` in use."""
+        self._need_store("fork")
+        if request_id not in self.stored and request_id not in self.parked:
+            raise ValueError(f"request id {request_id} is not parked or stored")
+        rid = self._next_id if new_id is None else new_id
+        if not 0 <= rid < 2 ** 32:
+            raise ValueError("request ids are uint32")
+        if rid in self._active:
+            raise ValueError(f"request id {rid} is already queued or running")
+        self.offload(request_id)
+        self.backend.fork_session(request_id, rid)
+        self.stored[rid] = self.stored[request_id]
+        share = self._share[rid] = self._share[request_id]
+        share[1].add(rid)
+        self._active.add(rid)
+        self._next_id = (rid + 1) % 2 ** 32 if new_id is None else self._next_id
+        return rid
+
+    def _free_slots(self) -> List[int]:
+        return sorted((s for s in range(self.max_batch) if self.live[s] is None and s not in self._held),
+                      key=lambda s: (self._last_admit[s], s))
+
+    def _restore(self) -> None:
+        """The store's part of a look: evictions, then the stored sessions whose continuation waits."""
+        self._looks += 1
+        want, free = len(self.stored_waiting) + len(self.queue), len(self._free_slots())
+        if want > free:
+            evict, nbytes = [], 0
+            for rid, (slot, rows, c) in sorted(self.parked.items(), key=lambda kv: (self._parked_at.get(kv[0], 0), kv[1][0])):
+                if len(evict) == want - free:
+                    break
+                b = self._session_bytes(slot, rows, c)
+                if self._fits(nbytes + b):
+                    evict.append(rid)
+                    nbytes += b
+            if evict:
+                self._save(evict)
+        free = self._free_slots()
+        batch = self.stored_waiting[:len(free)]
+        if not batch:
+            return
+        del self.stored_waiting[:len(batch)]
+        slots = free[:len(batch)]
+        self.backend.load_sessions(slots, [r.id for r in batch])
+        for s, r in zip(slots, batch):   # loaded: a parked slot whose continuation waits
+            r.slot, self._last_admit[s] = s, self._calls
+            self._held.add(s)
+            self._unshare(r.id, r.share)
+            r.share = None
+            self.backend.drop_session(r.id)
+            self.continuations.append(r)
+        self._calls += 1
+        self.loads.append([(r.id, s) for s, r in zip(slots, batch)])
 
     def _extend(self) -> None:
         while self.continuations:
@@ -910,11 +1060,15 @@ class SlotScheduler:
         """Run until nothing is queued and nothing is running, yielding (id, tokens) of each request as it retires or
         is parked; parked sessions do not keep it alive.  Raises RuntimeError when new requests wait, nothing runs and
         every slot is parked: nothing could ever change."""
-        while self.queue or self.continuations or any(r is not None for r in self.live):
+        while self.queue or self.continuations or self.stored_waiting or any(r is not None for r in self.live):
+            if self.store:
+                self._restore()
             self._extend()
             self._admit()
             if all(r is None for r in self.live):
-                raise RuntimeError(f"{len(self.queue)} request(s) wait and every slot is parked: release a session")
+                n = len(self.queue) + len(self.stored_waiting)
+                raise RuntimeError(f"{n} request(s) wait and every slot is parked: release a session"
+                                   + (f" (store_bytes {self.store_bytes} leaves no room to store one)" if self.store else ""))
             tokens, finished = self.backend.run_chunk(self.look)
             self.steps += self.look
             for s, r in enumerate(self.live):
@@ -934,6 +1088,7 @@ class SlotScheduler:
                     if r.keep:   # an eos that was drawn is never stepped into the cache
                         rows = r.past + r.n + len(r.tokens) - (1 if r.tokens[-1] == eos_id else 0)
                         self.parked[r.id] = (s, rows, r.c)
+                        self._parked_at[r.id] = self._looks
                         self._held.add(s)
                     else:
                         self._active.discard(r.id)
@@ -1064,6 +1219,20 @@ def score_groups(lens: List[int], max_admit: int, max_admit_tokens: int) -> List
     return groups
 
 
+@dataclass
+class _StoredSession:
+    """A session in the store: its blob in HBM, the host's copy of the blob's header, and the host records that travel
+    with it (``ContinuousGenerator.save_sessions``)."""
+    blob: torch.Tensor
+    hdr: "L.SessionHdr"
+    rid: int                 # the id it draws under
+    cap: int                 # the caption rows of its admission (_cap_host)
+    sp: Optional[SamplingParams] = None
+    hist_host: Optional[list] = None
+    ruled: bool = False
+    fork: bool = False       # loaded under ``rid`` in place of the id in the blob
+
+
 class ContinuousGenerator:
     """In-flight batching over ``max_batch`` cache slots: requests are prefilled into free slots while the others keep
     decoding, every step runs over all slots, and a request's result does not depend on what it ran beside (bitwise
@@ -1098,16 +1267,30 @@ class ContinuousGenerator:
     leaves the scores [0, -inf, ...], and every round is ergm_beam_select, ergm_beam_gather and the slot step over all
     rows (ergm_decode_run_slot_beams on the executor engines), so a group ends on the device at eos on every beam or at
     its bound and is served again at the next look (``BeamScheduler``).  ``submit`` takes the logit rules per request,
-    ``run_beams`` / ``drain_beams`` / ``beam_search`` serve the queue, and the sampled entry points are refused."""
+    ``run_beams`` / ``drain_beams`` / ``beam_search`` serve the queue, and the sampled entry points are refused.
+
+    ``session_store=True`` (not with ``num_beams``): more open conversations than slots.  A parked session's state (its
+    cache rows, caption rows, draw counters, controls, seen row, rule state and history) is packed into one blob in HBM
+    (ergm_slots_save; a ``torch.uint8`` tensor allocated on the generator's stream), which frees the slot, and unpacked
+    into any free slot when its next turn arrives (ergm_slots_load), all enqueued on the generator's stream between
+    chunks.  The scheduler evicts the least recently parked sessions when requests wait for slots
+    (``SlotScheduler(store=True)``); ``offload`` does it at once, ``fork_request`` gives a second id the same history,
+    ``extend_request`` and ``release`` take stored ids, and ``session_store_bytes`` caps what the store may hold.
+    ``save_calls`` / ``load_calls`` / ``stored_bytes`` count.  With ``session_store=False`` nothing changes."""
 
     ENGINES = BatchedGenerator.ENGINES
     num_beams: Optional[int] = None   # beam mode: the beams per request, fixed for the generator's life
 
     def __init__(self, model, max_batch: int, max_len: int, cap_max: int, engine: str = "python",
                  max_admit: Optional[int] = None, max_admit_tokens: Optional[int] = None, keep_logits: bool = False,
-                 controls: bool = False, bad_words_cap: int = 64, num_beams: Optional[int] = None):
+                 controls: bool = False, bad_words_cap: int = 64, num_beams: Optional[int] = None,
+                 session_store: bool = False, session_store_bytes: Optional[int] = None):
         if engine not in self.ENGINES:
             raise ValueError(f"engine {engine!r} is not one of {sorted(self.ENGINES)}")
+        if session_store and num_beams is not None:
+            raise ValueError("session_store and num_beams do not go together: beam mode has no sessions")
+        if session_store_bytes is not None and not session_store:
+            raise ValueError("session_store_bytes needs session_store=True")
         if num_beams is not None:
             if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
                 raise ValueError(f"num_beams {num_beams!r} outside [1, 8]")
@@ -1130,7 +1313,8 @@ class ContinuousGenerator:
         if max_admit_tokens is None:
             max_admit_tokens = min(2048, max_batch * max_len)
         if num_beams is None:
-            self.sched = SlotScheduler(self, max_batch, max_len, cap_max, max_admit, max_admit_tokens)
+            self.sched = SlotScheduler(self, max_batch, max_len, cap_max, max_admit, max_admit_tokens,
+                                       store=bool(session_store), store_bytes=session_store_bytes)
         else:   # the same policy over groups of num_beams slots
             self.n_groups = max_batch // num_beams
             self.sched = BeamScheduler(self, self.n_groups, num_beams, max_len, cap_max, max_admit, max_admit_tokens)
@@ -1184,6 +1368,12 @@ class ContinuousGenerator:
             self._slot_sp: List[Optional[SamplingParams]] = [None] * mb   # what each slot was last given
             self._lp_acc: List[Optional[list]] = [None] * mb              # the log-probabilities of the turn so far
             self._hist_host: List[list] = [[] for _ in range(mb)]   # what each slot's cache holds, as segments
+        self.session_store = bool(session_store)
+        self._rid_host = [0] * mb   # the id each slot draws under (a stored session takes it along)
+        self._store: dict = {}      # session id -> _StoredSession
+        self.save_calls = 0
+        self.load_calls = 0
+        self._session_state = None
         if engine != "python":
             self._create_plan()
 
@@ -1341,8 +1531,8 @@ class ContinuousGenerator:
         q0 = [sum(lens[:b]) for b in range(n_seq)]
         c0 = [sum(clens[:b]) for b in range(n_seq)]
         self.admit_calls += 1
-        for sl, c in zip(slots, clens):
-            self._cap_host[sl] = c
+        for sl, c, rid in zip(slots, clens, rids):
+            self._cap_host[sl], self._rid_host[sl] = c, rid
         if self.engine == "python":
             self._admit_python(slots, ids_l, tt_l, cap_l, lens, clens, q0, c0, max_new, rids, vis, aud, has)
         else:
@@ -1773,8 +1963,212 @@ class ContinuousGenerator:
         return self.sched.extend(request_id, int(ids.numel()), max_new_tokens, (ids, token_types), keep, sampling=sampling)
 
     def release(self, request_id: int) -> None:
-        """Free the slot of a parked request."""
+        """Free the slot of a parked request, or forget a stored one."""
         self.sched.release(request_id)
+
+    # ---- the session store: parked conversations leave their slots (session_store=True) --------------------------
+    def _need_store(self, what: str) -> None:
+        if not self.session_store:
+            raise ValueError(f"{what} needs ContinuousGenerator(session_store=True)")
+
+    def _sessions(self) -> "ops.SessionState":
+        """The bound buffers as ergm_session_state, built once."""
+        if self._session_state is None:
+            self._session_state = ops.SessionState(
+                self.kv, self.xkv, self.lens, self.cap_lens, self.stop_lens, self.finished, self.row_ids, self.row_steps,
+                ctl=self._ctl if self.controls else None, rules=self._rules if self.controls else None,
+                max_len=self.max_len, cap_max=self.cap_max)
+        return self._session_state
+
+    def _slot_flags(self, slot: int) -> int:
+        """The sections the session in ``slot`` takes along: its controls, and its rule state when it carries a rule."""
+        if not self.controls:
+            return 0
+        return L.SESSION_CTL | (L.SESSION_RULES if self._slot_ruled[slot] else 0)
+
+    def session_bytes(self, slot: int, rows: int, c: int) -> int:
+        """The size of the blob the session parked in ``slot`` with ``rows`` cache rows and ``c`` caption rows packs into."""
+        return self._sessions().bytes(rows, c, self._slot_flags(slot))
+
+    @property
+    def stored_bytes(self) -> int:
+        """The bytes of HBM the stored sessions hold; a fork shares its origin's blob."""
+        return sum(b.numel() for b in {id(r.blob): r.blob for r in self._store.values()}.values())
+
+    def _check_slots(self, slots, what: str) -> List[int]:
+        slots = [int(s) for s in slots]
+        if not slots or len(set(slots)) != len(slots) or min(slots) < 0 or max(slots) >= self.max_batch:
+            raise ValueError(f"{what}: slots {slots}: none, outside [0, {self.max_batch}) or named twice")
+        return slots
+
+    @torch.no_grad()
+    def save_sessions(self, slots, ids, rows=None, cap_rows=None) -> None:
+        """Pack the sessions parked in ``slots`` away under ``ids``, one blob in HBM each (the layout: ergm_hip.h,
+        "Session store"), and leave the slots idle and their host records as a new tenant finds them.  ``rows`` /
+        ``cap_rows``: the rows each slot holds (default: the scheduler's record of the parked ids).  "native" /
+        "fused": ergm_slots_save, 3 launches whatever the number of sessions; "python": the same bytes by torch slicing."""
+        self._need_store("save_sessions")
+        slots, ids = self._check_slots(slots, "save_sessions"), [int(i) for i in ids]
+        if rows is None or cap_rows is None:
+            for s, i in zip(slots, ids):
+                if i not in self.sched.parked or self.sched.parked[i][0] != s:
+                    raise ValueError(f"save_sessions: request id {i} is not parked in slot {s}")
+            rows, cap_rows = [self.sched.parked[i][1] for i in ids], [self.sched.parked[i][2] for i in ids]
+        rows, cap_rows = [int(n) for n in rows], [int(c) for c in cap_rows]
+        if not (len(slots) == len(ids) == len(rows) == len(cap_rows)) or len(set(ids)) != len(ids):
+            raise ValueError("save_sessions takes one distinct id, one row count and one caption row count per slot")
+        for i, n, c in zip(ids, rows, cap_rows):
+            if i in self._store:
+                raise ValueError(f"save_sessions: session id {i} is stored already")
+            if not (1 <= n <= self.max_len and 1 <= c <= self.cap_max):
+                raise ValueError(f"save_sessions: {n} rows / {c} caption rows outside [1, max_len {self.max_len}] / "
+                                 f"[1, cap_max {self.cap_max}]")
+        st = self._sessions()
+        flags = [self._slot_flags(s) for s in slots]
+        if self.engine == "python":
+            blobs = [self._pack_python(s, n, c, f) for s, n, c, f in zip(slots, rows, cap_rows, flags)]
+        else:
+            blobs = ops.slots_save(st, slots, rows, cap_rows, flags)
+        self.save_calls += 1
+        for s, i, n, c, f, blob in zip(slots, ids, rows, cap_rows, flags, blobs):
+            rec = _StoredSession(blob, st.header(n, c, f), self._rid_host[s], self._cap_host[s])
+            self._cap_host[s] = 0
+            if self.controls:
+                rec.sp, rec.hist_host, rec.ruled = self._slot_sp[s], self._hist_host[s], self._slot_ruled[s]
+                self._slot_sp[s], self._hist_host[s], self._lp_acc[s] = None, [], None
+                self._slot_ruled[s] = self._rule_live[s] = False
+            self._store[i] = rec
+
+    @torch.no_grad()
+    def load_sessions(self, slots, ids) -> None:
+        """Unpack the stored sessions ``ids`` into the free ``slots`` and leave them parked there (lens = stop_lens = the
+        rows, finished), with their host records; the stored copies stay until ``drop_session``.  A fork is loaded under
+        its own id, so its draws differ from its origin's."""
+        self._need_store("load_sessions")
+        slots, ids = self._check_slots(slots, "load_sessions"), [int(i) for i in ids]
+        if len(ids) != len(slots) or any(i not in self._store for i in ids):
+            raise ValueError(f"load_sessions: one stored id per slot (ids {ids}, stored {sorted(self._store)})")
+        recs = [self._store[i] for i in ids]
+        if self.engine == "python":
+            for s, rec in zip(slots, recs):
+                self._unpack_python(s, rec)
+        else:
+            row_ids = None
+            if any(rec.fork for rec in recs):
+                row_ids = torch.tensor([_u32_as_i32(rec.rid) for rec in recs], dtype=torch.int32).to(self.dev)
+            ops.slots_load(self._sessions(), slots, [rec.hdr for rec in recs], [rec.blob for rec in recs], row_ids)
+        self.load_calls += 1
+        for s, rec in zip(slots, recs):
+            self._cap_host[s], self._rid_host[s] = rec.cap, rec.rid
+            if self.controls:
+                self._slot_sp[s], self._hist_host[s], self._slot_ruled[s] = rec.sp, list(rec.hist_host), rec.ruled
+                self._rule_live[s], self._lp_acc[s] = False, None
+
+    def drop_session(self, session_id: int) -> None:
+        """Forget a stored session; its blob is freed with its last user."""
+        if self._store.pop(session_id, None) is None:
+            raise ValueError(f"session id {session_id} is not stored")
+
+    def fork_session(self, session_id: int, new_id: int) -> None:
+        """A second stored session ``new_id`` with the contents of ``session_id``: blobs are never written after the
+        save, so both ids share one tensor; the fork draws under ``new_id``."""
+        if session_id not in self._store or new_id in self._store:
+            raise ValueError(f"fork_session: id {session_id} is not stored, or id {new_id} is")
+        self._store[new_id] = replace(self._store[session_id], rid=int(new_id), fork=True)
+
+    def _pack_python(self, slot: int, n: int, c: int, flags: int) -> torch.Tensor:
+        """The yardstick of ergm_slots_save for one slot: the same blob, byte for byte, by torch slicing."""
+        st, nl, dev = self._sessions(), self.L, self.dev
+        rb, i32 = st.row_bytes, torch.int32
+        up16 = lambda x: (x + 15) & ~15
+        nbytes = st.bytes(n, c, flags)
+        blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        words = [L.SESSION_MAGIC, 1, flags, nl, rb, n, c, 0, 0, st.ld_seen if flags & L.SESSION_CTL else 0,
+                 st.bad_cap if flags & L.SESSION_RULES else 0, 0, nbytes & 0xFFFFFFFF, nbytes >> 32, 0, 0]
+        hdr = blob[:64].view(i32)
+        hdr.copy_(torch.tensor([_u32_as_i32(w) for w in words], dtype=i32))
+        hdr[7:8].copy_(self.row_ids[slot:slot + 1])
+        hdr[8:9].copy_(self.row_steps[slot:slot + 1])
+        o = 64
+        for caches, rows in ((self.kv, n), (self.xkv, c)):
+            sec = blob[o:o + nl * rows * rb].view(caches[0].dtype).view(nl, rows, -1)
+            for l in range(nl):
+                sec[l].copy_(caches[l][slot, :rows])
+            o += nl * rows * rb
+        if flags & L.SESSION_CTL:
+            w = blob[o:o + 32].view(i32)
+            w[:4].copy_(self._ctl_vals[:, slot])
+            w[4:5].copy_(self.min_step[slot:slot + 1])
+            o += 32
+            blob[o:o + 4 * st.ld_seen].view(i32).copy_(self.seen[slot])
+            o += up16(4 * st.ld_seen)
+        if flags & L.SESSION_RULES:
+            blob[o:o + 8].view(i32).copy_(self._rule_vals[:, slot])
+            o += 16
+            blob[o:o + 4 * st.bad_cap].view(i32).copy_(self._bad_pool[slot])
+            o += up16(4 * st.bad_cap)
+            blob[o:o + 4 * n].view(i32).copy_(self.hist[slot, :n])
+            o += up16(4 * n)
+            self._rule_vals[:, slot] = 0   # the next tenant inherits no rule
+            self._bad_pool[slot] = 0
+        assert o == nbytes
+        self.finished[slot] = 1
+        self.lens[slot] = 0
+        self.cap_lens[slot] = 0
+        return blob
+
+    def _unpack_python(self, slot: int, rec: "_StoredSession") -> None:
+        """The yardstick of ergm_slots_load for one slot, by torch slicing."""
+        st, nl, blob, h = self._sessions(), self.L, rec.blob, rec.hdr
+        rb, i32 = st.row_bytes, torch.int32
+        up16 = lambda x: (x + 15) & ~15
+        n, c, flags = h.rows, h.cap_rows, h.flags
+        if (h.magic, h.version, h.n_layer, h.row_bytes) != (L.SESSION_MAGIC, 1, nl, rb) or blob.numel() < st.bytes(n, c, flags):
+            raise ValueError("load_sessions: the blob's header disagrees with this generator")
+        hdr = blob[:64].view(i32)
+        o = 64
+        for caches, rows in ((self.kv, n), (self.xkv, c)):
+            sec = blob[o:o + nl * rows * rb].view(caches[0].dtype).view(nl, rows, -1)
+            for l in range(nl):
+                caches[l][slot, :rows].copy_(sec[l])
+            o += nl * rows * rb
+        self.lens[slot] = n
+        self.cap_lens[slot] = c
+        self.stop_lens[slot] = n
+        self.finished[slot] = 1
+        self.row_steps[slot:slot + 1].copy_(hdr[8:9])
+        if rec.fork:
+            self.row_ids[slot] = _u32_as_i32(rec.rid)
+        else:
+            self.row_ids[slot:slot + 1].copy_(hdr[7:8])
+        if flags & L.SESSION_CTL:
+            w = blob[o:o + 32].view(i32)
+            self._ctl_vals[:, slot] = w[:4]
+            self.min_step[slot:slot + 1].copy_(w[4:5])
+            o += 32
+            self.seen[slot].copy_(blob[o:o + 4 * st.ld_seen].view(i32))
+            o += up16(4 * st.ld_seen)
+        if flags & L.SESSION_RULES:
+            self._rule_vals[:, slot] = blob[o:o + 8].view(i32)
+            o += 16
+            self._bad_pool[slot].copy_(blob[o:o + 4 * st.bad_cap].view(i32))
+            o += up16(4 * st.bad_cap)
+            self.hist[slot, :n].copy_(blob[o:o + 4 * n].view(i32))
+        elif self.controls:   # a session without a rule turns off what the slot's last tenant left
+            self._rule_vals[:, slot] = 0
+            self._bad_pool[slot] = 0
+
+    def offload(self, request_id: int) -> None:
+        """Move a parked session out of its slot into the store at once (a stored id is left as it is); the slot is
+        free for the next admission.  ValueError for an id that is neither parked nor stored."""
+        self._need_store("offload")
+        self.sched.offload(request_id)
+
+    def fork_request(self, request_id: int, new_id: Optional[int] = None) -> int:
+        """A second session with the history of ``request_id`` (parked: it is offloaded first), returned under ``new_id``
+        (default: the next id).  ``extend_request`` continues either; the fork draws under its own id."""
+        self._need_store("fork_request")
+        return self.sched.fork(request_id, new_id)
 
     def drain(self, top_p: float, eos_id: int, sp2_id: int, seed: int = 0):
         """Serve the queue, yielding (id, tokens) as each request retires."""

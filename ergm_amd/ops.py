@@ -755,6 +755,124 @@ def hist_follow(hist, parent, lens, W: int, max_len: int):
            _stream(hist.device))
 
 
+def session_bytes(n_layer: int, row_bytes: int, rows: int, cap_rows: int, ld_seen: int = 0, bad_cap: int = 0, flags: int = 0) -> int:
+    """The size of a session blob (ergm_session_bytes; host only).  ValueError for arguments it rejects."""
+    n = L.load().ergm_session_bytes(n_layer, row_bytes, rows, cap_rows, ld_seen, bad_cap, flags)
+    if n == 0:
+        raise ValueError(f"session_bytes: bad shape n_layer {n_layer} row_bytes {row_bytes} rows {rows} cap_rows {cap_rows} "
+                         f"ld_seen {ld_seen} bad_cap {bad_cap} flags {flags}")
+    return n
+
+
+def session_header(n_layer: int, row_bytes: int, rows: int, cap_rows: int, ld_seen: int = 0, bad_cap: int = 0,
+                   flags: int = 0) -> L.SessionHdr:
+    """The host's copy of a blob's header (ergm_session_header): everything but the draw counters."""
+    h = L.SessionHdr()
+    L.call("ergm_session_header", n_layer, row_bytes, rows, cap_rows, ld_seen, bad_cap, flags, C.byref(h))
+    return h
+
+
+class SessionState:
+    """ergm_session_state over a generator's buffers: ``kv`` / ``xkv`` lists of per-layer caches [max_batch, rows, width]
+    with the same strides per list, the slot-state arrays (int32 [max_batch]; finished uint8), and optionally the
+    ``sample_ctl`` / ``rules_desc`` structs of the per-slot controls and rules.  Holds addresses only: the caller keeps
+    the tensors alive.  ``max_len`` / ``cap_max`` default to the caches' row counts."""
+
+    def __init__(self, kv, xkv, lens, cap_lens, stop_lens, finished, row_ids, row_steps, ctl: Optional[L.SampleCtl] = None,
+                 rules: Optional[L.LogitRules] = None, max_len: Optional[int] = None, cap_max: Optional[int] = None):
+        _need_gpu(lens, cap_lens, stop_lens, finished, row_ids, row_steps, *kv, *xkv)
+        k0, x0 = kv[0], xkv[0]
+        if len(kv) != len(xkv):
+            raise ValueError("session state: one caption cache per self-attention cache")
+        for group, c0 in ((kv, k0), (xkv, x0)):
+            for c in group:
+                assert c.dim() == 3 and c.dtype == k0.dtype and c.shape == c0.shape and c.stride() == c0.stride() and c.stride(2) == 1
+        assert k0.shape[0] == x0.shape[0] and k0.shape[2] == x0.shape[2]
+        mb = k0.shape[0]
+        for t in (lens, cap_lens, stop_lens, row_ids, row_steps):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= mb
+        assert finished.dtype == torch.uint8 and finished.is_contiguous() and finished.numel() >= mb
+        es = k0.element_size()
+        self.device, self.n_layer, self.row_bytes, self.max_batch = k0.device, len(kv), k0.shape[2] * es, mb
+        self.max_len = k0.shape[1] if max_len is None else max_len
+        self.cap_max = x0.shape[1] if cap_max is None else cap_max
+        if not (1 <= self.max_len <= k0.shape[1] and 1 <= self.cap_max <= x0.shape[1]):
+            raise ValueError("session state: max_len / cap_max outside the caches")
+        self._keep = (kv, xkv, lens, cap_lens, stop_lens, finished, row_ids, row_steps, ctl, rules,
+                      (C.c_void_p * len(kv))(*[c.data_ptr() for c in kv]), (C.c_void_p * len(xkv))(*[c.data_ptr() for c in xkv]))
+        self.ld_seen = 0 if ctl is None else ctl.ld_seen
+        self.bad_cap = 0 if rules is None else rules.ld_bad
+        self.flags = (L.SESSION_CTL if ctl is not None else 0) | (L.SESSION_RULES if rules is not None else 0)
+        self.c = L.SessionState(self._keep[10], self._keep[11], len(kv), self.row_bytes, k0.stride(0) * es, k0.stride(1) * es,
+                                x0.stride(0) * es, x0.stride(1) * es, mb, self.max_len, self.cap_max, lens.data_ptr(),
+                                cap_lens.data_ptr(), stop_lens.data_ptr(), finished.data_ptr(), row_ids.data_ptr(),
+                                row_steps.data_ptr(), None if ctl is None else C.pointer(ctl),
+                                None if rules is None else C.pointer(rules))
+
+    def bytes(self, rows: int, cap_rows: int, flags: int) -> int:
+        return session_bytes(self.n_layer, self.row_bytes, rows, cap_rows, self.ld_seen, self.bad_cap, flags)
+
+    def header(self, rows: int, cap_rows: int, flags: int) -> L.SessionHdr:
+        return session_header(self.n_layer, self.row_bytes, rows, cap_rows, self.ld_seen, self.bad_cap, flags)
+
+
+def session_meta(slots, rows, cap_rows, blobs, flags, device) -> torch.Tensor:
+    """The device meta of a save or a load: int64 [ERGM_SESSION_META_ROWS, n_seq], slot | rows | cap_rows | blob address
+    | flags | blob bytes; one copy to the device."""
+    return torch.tensor([list(slots), list(rows), list(cap_rows), [b.data_ptr() for b in blobs], list(flags),
+                         [b.numel() for b in blobs]], dtype=torch.int64).to(device)
+
+
+def _session_blobs(blobs):
+    for b in blobs:
+        _need_gpu(b)
+        assert b.dtype == torch.uint8 and b.is_contiguous()
+    n = len(blobs)
+    return (C.c_void_p * n)(*[b.data_ptr() for b in blobs]), (C.c_size_t * n)(*[b.numel() for b in blobs])
+
+
+def slots_save(state: SessionState, slots, rows, cap_rows, flags, blobs=None, meta=None):
+    """Pack the slots' state into one blob each and leave the slots idle (ergm_slots_save): ``slots`` / ``rows`` /
+    ``cap_rows`` / ``flags`` host ints per session, ``blobs`` uint8 tensors of at least ``state.bytes(...)`` each
+    (default: allocated here, on the current stream).  Returns the blobs."""
+    n = len(slots)
+    slots, rows, cap_rows, flags = ([int(v) for v in x] for x in (slots, rows, cap_rows, flags))
+    if not (n == len(rows) == len(cap_rows) == len(flags)) or n < 1:
+        raise ValueError("slots_save takes one row count, one caption row count and one flag word per slot")
+    if blobs is None:
+        blobs = [torch.empty(state.bytes(r, c, f), dtype=torch.uint8, device=state.device) for r, c, f in zip(rows, cap_rows, flags)]
+    if len(blobs) != n:
+        raise ValueError("slots_save takes one blob per slot")
+    ptrs, sizes = _session_blobs(blobs)
+    if meta is None:
+        meta = session_meta(slots, rows, cap_rows, blobs, flags, state.device)
+    assert meta.dtype == torch.int64 and meta.is_contiguous() and meta.shape == (L.SESSION_META_ROWS, n) and meta.is_cuda
+    arr = lambda v: (C.c_int * n)(*v)
+    L.call("ergm_slots_save", C.byref(state.c), n, arr(slots), arr(rows), arr(cap_rows), arr(flags), ptrs, sizes, _ptr(meta),
+           _stream(state.device))
+    return blobs
+
+
+def slots_load(state: SessionState, slots, hdrs, blobs, row_ids=None, meta=None):
+    """Unpack blobs into slots and leave the slots parked (ergm_slots_load): ``hdrs`` the host's ``SessionHdr`` of every
+    blob, ``row_ids`` (int32 [n_seq] on the device, uint32 bits; optional) the ids the sessions draw under in place of
+    the ones they were saved with."""
+    n = len(slots)
+    slots = [int(s) for s in slots]
+    if not (n == len(hdrs) == len(blobs)) or n < 1:
+        raise ValueError("slots_load takes one header and one blob per slot")
+    ptrs, sizes = _session_blobs(blobs)
+    if meta is None:
+        meta = session_meta(slots, [h.rows for h in hdrs], [h.cap_rows for h in hdrs], blobs, [h.flags for h in hdrs],
+                            state.device)
+    assert meta.dtype == torch.int64 and meta.is_contiguous() and meta.shape == (L.SESSION_META_ROWS, n) and meta.is_cuda
+    if row_ids is not None:
+        _need_gpu(row_ids)
+        assert row_ids.dtype == torch.int32 and row_ids.is_contiguous() and row_ids.numel() == n
+    L.call("ergm_slots_load", C.byref(state.c), n, (C.c_int * n)(*slots), (L.SessionHdr * n)(*hdrs), ptrs, sizes, _ptr(row_ids),
+           _ptr(meta), _stream(state.device))
+
+
 def feat_pool(x: torch.Tensor, lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """Mean over frames of encoder outputs x [B, T, D] (f32 / bf16, any row strides with unit
     last-dim stride) -> [B, D] f32; ``lengths`` [B] int32 limits each sample to its valid frames.

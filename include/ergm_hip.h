@@ -33,6 +33,8 @@
  *                         (src/model.py:739-746) and the ranking in front of it, on the device
  *   ergm_logit_rules_apply, ergm_hist_write, ergm_hist_append, ergm_hist_follow, ergm_decode_set_rules (same version)
  *                         no_repeat_ngram_size and bad_words_ids of generation, over a token history on the device
+ *   ergm_session_bytes, ergm_session_header, ergm_slots_save, ergm_slots_load (same version)
+ *                         no counterpart: a conversation's cache and sampler state leave and re-enter a slot
  *   ergm_linear_rows      Conv1D / lm_head for the few rows of a decode step, with the nn.LayerNorm in front
  *                         of it (src/model.py:298,318,332) computed in the same launch
  *   ergm_decode_*         the token loop of nucleus_sampling (src/main.py:253-282) for a batch, after the
@@ -1073,6 +1075,93 @@ int ergm_decode_score(ergm_decode_plan* plan, int n_seq, const int* lens, const 
                       const float* aud, const uint8_t* has_feat, const int64_t* targets, float* logprob, int* top1,
                       void* workspace, size_t ws_bytes, void* stream);
 int ergm_decode_score_launches(const ergm_decode_plan* plan, int n_seq, int rows, int cap_rows);
+
+/* ---- Session store: a slot's state as one blob in HBM (found by symbol, ABI unchanged) -------------------------------
+ * A parked conversation leaves its cache slot as one compact blob and returns into any free slot.  What travels is the
+ * state of one slot: rows [0, n) of every layer's self-attention K | V, rows [0, c) of every layer's caption K | V, the
+ * draw counters, with ERGM_SESSION_CTL the slot's sampling controls and its whole `seen` row, with ERGM_SESSION_RULES the
+ * slot's rule values, its bad-word pool row and hist[slot][0 .. n).  n and c are the host's record of the rows the slot
+ * holds; the kernels clamp them to [0, max_len] / [0, cap_max] before an address is formed.  The logits do not travel.
+ *
+ * Blob layout (little endian; every section starts on a 16-byte boundary, padding bytes are written as 0):
+ *     0    header, 64 bytes = 16 words: magic "ERGS" 0x53475245 | version 1 | flags | n_layer | row_bytes | n | c |
+ *          row_ids[slot] | row_steps[slot] | ld_seen (0 without CTL) | bad_cap (0 without RULES) | 0 |
+ *          blob bytes, low word | high word | 0 | 0
+ *     64   self-attention K | V: layer l's row i at 64 + (l·n + i)·row_bytes
+ *          caption K | V behind it: layer l's row i at 64 + n_layer·n·row_bytes + (l·c + i)·row_bytes
+ *     CTL  8 words: top_p | temperature | rep_penalty (f32 bits) | top_k | min_step | 0 | 0 | 0;
+ *          then the seen row: ld_seen words, padded to 16 bytes
+ *     RULES 4 words: start | ngram | 0 | 0; then the pool row: bad_cap words padded to 16 bytes; then hist[slot][0 .. n):
+ *          n words padded to 16 bytes
+ * ergm_session_bytes: the blob's size, a multiple of 16; 0 for arguments it rejects (n_layer, rows, cap_rows < 1,
+ * row_bytes no positive multiple of 16, flags outside ERGM_SESSION_CTL | ERGM_SESSION_RULES, CTL with ld_seen < 1, RULES
+ * with bad_cap < 1; ld_seen / bad_cap are ignored without their flag).  Host only, as is ergm_session_header, which
+ * fills the caller's host copy of a header (row_ids / row_steps, which only the device knows, are left 0).
+ *
+ * ergm_session_state: the bound buffers.  kv / xkv: HOST arrays of n_layer device pointers, slot s of layer l at
+ * kv[l] + s·kv_ld_seq, its row i at + i·kv_ld_row (bytes, multiples of 16; ergm_beam_gather's layout), row_bytes each;
+ * the slot-state arrays of ergm_decode_bind_slots; ctl / rules: NULL, or the generator's per-slot arrays, every pointer of
+ * them set (they are written by a load; ld_seen words of a seen row and ld_bad words of a pool row travel).
+ *
+ * ergm_slots_save packs n_seq slots into n_seq blobs, session b of slot slots[b] with rows[b] / cap_rows[b] rows and the
+ * sections flags[b] names, and leaves each slot idle: finished = 1, lens = 0, cap_lens = 0; a slot saved with RULES also
+ * gets start = ngram = 0 and a zero pool row, so the next tenant inherits no rule.  ergm_slots_load unpacks blobs into
+ * slots: lens = n, cap_lens = c, stop_lens = n, finished = 1 (the parked state), row_steps, the controls and the rule
+ * values from the blob, row_ids from the blob or, when row_ids is given (device uint32 [n_seq]), from that array (a fork
+ * draws under its own id).  A blob without RULES loaded under a state with rules leaves start = ngram = 0 and a zero pool
+ * row.  A load writes nothing at or past row n / c of a cache, nothing of hist at or past n, nothing in another slot.
+ * hdrs: the caller's HOST copies of the blobs' headers, checked against `state` here; the device header supplies only
+ * the draw counters, which form no address.
+ *   meta_dev: DEVICE int64 [ERGM_SESSION_META_ROWS][n_seq]: slot | rows | cap_rows | blob address | flags | blob bytes,
+ *     the host arguments again for the kernels.  rows / cap_rows are clamped and flags masked by what `state` has; a
+ *     slot outside [0, max_batch), a zero address, or clamped sizes that give a blob above the stated bytes make the
+ *     kernels skip the session: no value makes a kernel follow an index out of a table or past the end of a blob.  The
+ *     blob address itself is followed as any pointer argument is.
+ * Kernels: a workgroup per (session, layer, 64-row chunk), a wave per cache row, 16 bytes per lane, the layer pointers in
+ * the kernel arguments (48 per launch), and one state kernel of a workgroup per session: 3 launches for up to 48 layers
+ * whatever n_seq is (ergm_session_launches).  Plain loads and stores, no atomics; one stream, nothing read back.
+ * ERGM_EINVAL before any launch: n_seq outside [1, max_batch]; a slot outside [0, max_batch) or named twice; rows outside
+ * [1, max_len]; cap_rows outside [1, cap_max]; flags naming a section `state` lacks (CTL also when `state` has controls
+ * and the flag is missing); a blob below ergm_session_bytes, NULL, not 16-byte aligned or (save) named twice; on load a
+ * header whose magic, version, n_layer, row_bytes, flags, ld_seen, bad_cap or size disagree with `state`; strides or
+ * row_bytes that are no multiples of 16 or shorter than the rows they span; a NULL or misaligned pointer.             */
+#define ERGM_SESSION_CTL 1
+#define ERGM_SESSION_RULES 2
+#define ERGM_SESSION_META_ROWS 6
+#define ERGM_SESSION_MAGIC 0x53475245u
+typedef struct {
+    uint32_t magic, version, flags;
+    int32_t n_layer, row_bytes, rows, cap_rows;
+    uint32_t row_id, row_steps;
+    int32_t ld_seen, bad_cap, reserved0;
+    uint64_t bytes;
+    uint32_t reserved1[2];
+} ergm_session_hdr; /* 64 bytes */
+typedef struct {
+    void* const* kv;
+    void* const* xkv;
+    int n_layer;
+    int row_bytes;
+    int64_t kv_ld_seq, kv_ld_row, xkv_ld_seq, xkv_ld_row;
+    int max_batch, max_len, cap_max;
+    int* lens;
+    int* cap_lens;
+    int* stop_lens;
+    uint8_t* finished;
+    uint32_t* row_ids;
+    uint32_t* row_steps;
+    const ergm_sample_ctl* ctl;     /* NULL: no control section */
+    const ergm_logit_rules* rules;  /* NULL: no rule section */
+} ergm_session_state;
+size_t ergm_session_bytes(int n_layer, int row_bytes, int rows, int cap_rows, int ld_seen, int bad_cap, int flags);
+int ergm_session_header(int n_layer, int row_bytes, int rows, int cap_rows, int ld_seen, int bad_cap, int flags,
+                        ergm_session_hdr* out);
+int ergm_session_launches(int n_layer);
+int ergm_slots_save(const ergm_session_state* state, int n_seq, const int* slots, const int* rows, const int* cap_rows,
+                    const int* flags, void* const* blobs, const size_t* blob_bytes, const int64_t* meta_dev, void* stream);
+int ergm_slots_load(const ergm_session_state* state, int n_seq, const int* slots, const ergm_session_hdr* hdrs,
+                    void* const* blobs, const size_t* blob_bytes, const uint32_t* row_ids, const int64_t* meta_dev,
+                    void* stream);
 
 /* Library information and errors. */
 int ergm_version(void);

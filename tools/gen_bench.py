@@ -54,11 +54,15 @@ Beam search on the slots, ``--beams W --requests [--engines pyt
 beam search, per engine, as static arrival-order batches of 32 // W prompts (BatchedGenerator.beam_search, each batch to
 its largest bound) and through one beam-mode ContinuousGenerator of 32 slots, alternating in one process, median of 5
 after a warm-up: requested tokens/s, rounds and rounds per requested token of both, and the seed launch alone.
+--case store: the session store.  First ergm_slots_save / ergm_slots_load against the "python"
+engine's torch slicing for 1 / 8 / 32 sessions of 128 and 1,023 cache rows (HIP events, alternating, µs and GB/s of
+bytes read + written); then 128 four-turn sessions on 32 slots with the turn shape of --case turns, the store against
+re-submitting the history every turn, on "native" and "fused".
 Without --case the tool runs every case in turn, each in a fresh child process under its own timeout, one at a
 time, and stops at the first that fails.  --cases a,b,c runs those cases in that
 order (e.g. b32,n32,f32,b32,n32,f32 to alternate engines on one box).  For the kernel-time split of one engine:
   rocprofv3 --kernel-trace --stats -d OUT -- python tools/gen_bench.py --case f32
-Usage (GPU box): python tools/gen_bench.py [--case kv|b1|b8|b32|n*|f*|attn|bs32|bc32|bd32|bx32|n?32|f?32|admit|turns|sample]
+Usage (GPU box): python tools/gen_bench.py [--case kv|b1|b8|b32|n*|f*|attn|bs32|bc32|bd32|bx32|n?32|f?32|admit|turns|sample|store]
                  [--cases LIST]"""
 import json
 import os
@@ -70,7 +74,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 ENGINES = {"b": "python", "n": "native", "f": "fused"}
 CASES = {"kv": 240, **{e + b: 240 for e in ENGINES for b in ("1", "8", "32")}, "attn": 240,   # seconds a child may take
-         **{e + m + "32": 300 for e in ENGINES for m in "scdxrw"}, "admit": 240, "turns": 420, "sample": 240}
+         **{e + m + "32": 300 for e in ENGINES for m in "scdxrw"}, "admit": 240, "turns": 420, "sample": 240,
+         "store": 1100}
 N_REQ, REQ_MEAN = 256, 16
 PROMPT = CAPS = NEW = 64
 TOP_P, NO_EOS, SP2 = 0.95, -1, 50259
@@ -329,6 +334,104 @@ def _turns():
         print(json.dumps(row), flush=True)
 
 
+STORE_SESSIONS, STORE_SLOTS = 128, 32
+
+
+def _store_kernels(dev, model):
+    """ergm_slots_save / ergm_slots_load against the "python" engine's torch slicing, HIP events, alternating: n sessions
+    of `rows` cache rows and CAPS caption rows of GPT-2 small; bytes = what a save reads and writes."""
+    import torch
+    from ergm_amd.generate import ContinuousGenerator
+    for rows in (128, 1023):
+        gens = {e: ContinuousGenerator(model, max_batch=32, max_len=1024, cap_max=CAPS, engine=e, session_store=True)
+                for e in ("python", "native")}
+        for g in gens.values():
+            for t in g.kv + g.xkv:
+                t.normal_()
+        for n in (1, 8, 32):
+            slots, ids = list(range(n)), list(range(n))
+            ms = {(e, op): [] for e in gens for op in ("save", "load")}
+            for rep in range(REPEATS + 1):
+                for e, g in gens.items():
+                    t_save = _event_ms(lambda: g.save_sessions(slots, ids, rows=[rows] * n, cap_rows=[CAPS] * n))
+                    t_load = _event_ms(lambda: g.load_sessions(slots, ids))
+                    nbytes = g.stored_bytes
+                    for i in ids:
+                        g.drop_session(i)
+                    if rep:
+                        ms[(e, "save")].append(t_save)
+                        ms[(e, "load")].append(t_load)
+            row = {"case": "store_kernels", "sessions": n, "rows": rows, "cap_rows": CAPS, "blob_bytes": nbytes}
+            for (e, op), v in ms.items():
+                med = statistics.median(v)
+                row[f"{e}_{op}"] = {"us_median": round(med * 1e3, 1), "us_all": [round(x * 1e3, 1) for x in v],
+                                    "GB_per_s": round(2 * nbytes / med / 1e6, 1)}
+            print(json.dumps(row), flush=True)
+
+
+def _store():
+    """128 four-turn sessions on 32 slots with the turn shape of --case turns: the session store against re-submitting
+    the whole history every turn, which is all a generator without a store offers for more sessions than slots."""
+    import torch
+    from ergm_amd.generate import ContinuousGenerator
+    dev, model, prompts, _ = _setup_requests(STORE_SESSIONS)
+    _store_kernels(dev, model)
+    g = torch.Generator().manual_seed(3)
+    later = [[(torch.randint(0, 50000, (TURN_ROWS,), generator=g).to(dev), torch.full((TURN_ROWS,), SP2 - 1, device=dev))
+              for _ in range(STORE_SESSIONS)] for _ in range(TURNS - 1)]
+    max_len = (PROMPT + TURN_NEW + (TURNS - 1) * (TURN_ROWS + TURN_NEW) + 63) // 64 * 64
+    sample = dict(top_p=TOP_P, eos_id=NO_EOS, sp2_id=SP2, seed=7)
+    for engine in ("native", "fused"):
+        kw = dict(max_batch=STORE_SLOTS, max_len=max_len, cap_max=CAPS, engine=engine)
+        stored, plain = ContinuousGenerator(model, session_store=True, **kw), ContinuousGenerator(model, **kw)
+        moved = [0]
+
+        def run_store():
+            c0 = (stored.save_calls, stored.load_calls)
+            moved[0] = 0
+            ids = [stored.submit(p, TURN_NEW, keep=True) for p in prompts]
+            stored.run(**sample)
+            for t in range(TURNS - 1):
+                for i, (x, tt) in zip(ids, later[t]):
+                    stored.extend_request(i, x, tt, TURN_NEW)
+                out = stored.run(**sample)
+                assert all(len(out[i]) == TURN_NEW for i in ids)
+            moved[0] = stored.stored_bytes   # what the store holds when the last turn has run
+            for i in ids:
+                stored.release(i)
+            return stored.save_calls - c0[0], stored.load_calls - c0[1]
+
+        def run_resubmit():
+            hist = [(p[0], p[1]) for p in prompts]
+            for t in range(TURNS):
+                if t:
+                    hist = [(torch.cat([h[0], torch.tensor([new[i]], device=dev), later[t - 1][b][0].view(1, -1)], 1),
+                             torch.cat([h[1], torch.full((1, TURN_NEW), SP2, device=dev), later[t - 1][b][1].view(1, -1)], 1))
+                            for b, (h, i) in enumerate(zip(hist, ids))]
+                ids = [plain.submit((h[0], h[1], p[2], None, None), TURN_NEW) for h, p in zip(hist, prompts)]
+                new = plain.run(**sample)
+                assert all(len(new[i]) == TURN_NEW for i in ids)
+
+        ms, calls = {"store": [], "resubmit": []}, (0, 0)
+        for rep in range(REPEATS + 1):   # alternating; the first of each is the warm-up
+            for name, fn in (("store", run_store), ("resubmit", run_resubmit)):
+                res = []
+                t = _event_ms(lambda: res.append(fn()))
+                if name == "store":
+                    calls = res[0]
+                if rep:
+                    ms[name].append(t)
+        tokens = STORE_SESSIONS * TURNS * TURN_NEW
+        row = {"case": "store", "engine": engine, "sessions": STORE_SESSIONS, "slots": STORE_SLOTS, "turns": TURNS,
+               "requested_tokens": tokens, "save_calls": calls[0], "load_calls": calls[1], "stored_bytes_at_end": moved[0]}
+        for name in ms:
+            med = statistics.median(ms[name])
+            row[name] = {"ms_median": round(med, 2), "ms_all": [round(x, 2) for x in ms[name]],
+                         "tokens_per_s": round(tokens / med * 1e3, 1)}
+        row["speedup"] = round(statistics.median(ms["resubmit"]) / statistics.median(ms["store"]), 3)
+        print(json.dumps(row), flush=True)
+
+
 BEAM_EOS = 50258   # a special token the random model's beams do not reach: every search runs to the bound
 
 
@@ -545,6 +648,8 @@ def main():
             _turns()
         elif case == "sample":
             _sampler()
+        elif case == "store":
+            _store()
         elif len(case) == 4 and case[1] in "scdxrw":
             _requests(case)
         else:
